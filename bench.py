@@ -2,9 +2,15 @@
 """Headline benchmark: SLAM frames/sec (TUM fr1_desk-shaped 512x384 frames)
 + Msplats/sec rasterized, on 1..8 MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \\
       --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes the last timed
+step's outputs when --dump-outputs is given and prints the result line.
+Every other leg described below (per-kernel profile and roofline, end-to-end,
+live camera, keyframe pairs, backend, C5 map, C3 raster, retrieval, CPU
+baseline) runs only with --full, after the timed region.
 
 A step is one frame of the reference's main loop in TRACKING mode
 (main.py:451-506 with --no-viz, rendering on, spatial stride 4):
@@ -18,7 +24,7 @@ frames of all ranks / max-over-ranks wall time.  The keyframe-pair batch
 (the unit that does shard) is reported beside it by
 splatt3r_amd/pairs.py through the sharded FactorGraph.add_factors path.
 
-Further legs on rank 0 (N = 1): `backend` -- the same frontend with the
+Further legs on rank 0 (N = 1, --full): `backend` -- the same frontend with the
 reference's backend running concurrently on a worker thread / HIP stream
 (base.yaml single_thread: False: retrieval + add_factors + GN per
 keyframe), reported as a second frames/s; `map_c5` -- the full-map render
@@ -62,6 +68,14 @@ def _args(argv=None):
                          "bench.py starts N worker processes itself")
     ap.add_argument("--steps", type=int, default=120)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (per-kernel profile and "
+                         "roofline, end-to-end, live camera, keyframe pairs, backend, C5 map, "
+                         "C3 raster, retrieval, CPU baseline); the --no-* options below pick "
+                         "among them.  Without it only the headline's frame loop runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned "
+                         "(rank 0: pose, fused pointmap, confidence, render) as DIR/<name>.npy")
     ap.add_argument("--cpu-frames", type=int, default=2,
                     help="frames of the CPU restatement timed for cpu_baseline (rank 0, N=1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -113,7 +127,33 @@ def _args(argv=None):
     ap.add_argument("--dist-dry-run", action="store_true",
                     help="CPU check of the launch path: spawn / rendezvous (gloo) / barrier / "
                          "max over ranks / pair sharding, no GPU work (tests/test_bench_plan.py)")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if not a.full and not a.dist_dry_run:
+        # a plain run: the headline's frame loop alone (the dry run times
+        # nothing: it walks the launch path of every sharded leg)
+        for leg in _FULL_LEGS:
+            setattr(a, "no_" + leg, True)
+    return a
+
+
+# the legs beside the headline (each has a --no-<leg> option), run with --full
+_FULL_LEGS = ("cpu_baseline", "c3", "pairs", "backend", "map", "e2e", "live", "kprof",
+              "in_window")
+
+
+def dump_outputs(path, frame, render):
+    """--dump-outputs: what the last timed Frontend.step handed back, one
+    float32 .npy each: the tracked Frame's pose (Sim3 data: t, q xyzw, s),
+    fused canonical pointmap and confidence, and the frame's Gaussian render
+    as read back to the host (H x W x 3).  ~5 MB at 512x384."""
+    os.makedirs(path, exist_ok=True)
+    out = {"pose": frame.T_WC.data, "pointmap": frame.X_canon, "confidence": frame.C,
+           "render": render}
+    for name, t in out.items():
+        if t is None:
+            continue
+        arr = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 # S3_PLAN_OVERLAP=0: the first exact plan of the search (round-4 driver runs;
@@ -1114,9 +1154,10 @@ def main(argv=None):
             gc_log.append((info.get("generation"), len(host_ms),
                            round((time.perf_counter() - gc_t[0]) * 1e3, 3)))
     gc.callbacks.append(_gc_cb)
+    last = None
     for i in range(a.warmup + 1, nfr):
         h0 = time.perf_counter()
-        fe.step(i, frames[i], next_img=nxt(i))
+        last = fe.step(i, frames[i], next_img=nxt(i))
         host_ms.append(round((time.perf_counter() - h0) * 1e3, 3))
     fe.drain()                             # every frame's render issued
     torch.cuda.synchronize()
@@ -1132,6 +1173,8 @@ def main(argv=None):
             print(out.getvalue(), file=__import__("sys").stderr)
     _barrier(ws)
     t_max = _max_over_ranks(t, ws, dev)
+    if a.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(a.dump_outputs, last, fe.last_render)
     ev = model.encoder.events
     model.encoder.events = None
     encodes = _encodes(model.encoder) - enc0

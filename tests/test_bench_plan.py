@@ -6,7 +6,9 @@
   steps, each replay holds at most enc_batch images, every frame is encoded
   exactly once, and the frames the bench allocates suffice;
 * `--gpus 2` without an external launcher spawns two ranks that meet over
-  gloo (--dist-dry-run), shard a pair list and report world size and backend.
+  gloo (--dist-dry-run), shard a pair list and report world size and backend;
+* a plain run keeps only the headline's frame loop, `--full` every other leg,
+  and `--dump-outputs` writes the last timed step's arrays as float32 .npy.
 """
 import json
 import os
@@ -118,3 +120,41 @@ def test_driver_plan_overlaps_every_timed_replay():
     assert sum(c for _, _, c in queued) == steps
     assert all(s - i >= ahead for i, s, _ in queued)
     assert queued[-1][0] < warmup + steps
+
+
+def test_plain_run_is_the_headline_alone_and_full_keeps_every_leg():
+    """Without --full every leg beside the frame loop is off; with it the
+    --no-<leg> options decide; the dry run keeps its sharded-leg walk."""
+    a = bench._args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert (a.steps, a.warmup, a.dump_outputs, a.full) == (20, 5, None, False)
+    assert all(getattr(a, "no_" + leg) for leg in bench._FULL_LEGS)
+    a = bench._args(["--full"])
+    assert not any(getattr(a, "no_" + leg) for leg in bench._FULL_LEGS)
+    a = bench._args(["--full", "--no-map", "--no-cpu-baseline"])
+    assert [leg for leg in bench._FULL_LEGS if getattr(a, "no_" + leg)] == ["cpu_baseline", "map"]
+    a = bench._args(["--gpus", "2", "--dist-dry-run"])
+    assert not a.no_backend
+
+
+def test_dump_outputs_writes_float32_arrays(tmp_path):
+    import types
+
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(0)
+    frame = types.SimpleNamespace(
+        T_WC=types.SimpleNamespace(data=torch.randn(1, 8, generator=g)),
+        X_canon=torch.randn(12, 3, generator=g).half(), C=torch.rand(12, 1, generator=g))
+    render = torch.rand(4, 6, 3, generator=g)
+    out = tmp_path / "dump"
+    bench.dump_outputs(str(out), frame, render)
+    assert sorted(os.listdir(out)) == ["confidence.npy", "pointmap.npy", "pose.npy", "render.npy"]
+    for name, t in (("pose", frame.T_WC.data), ("pointmap", frame.X_canon),
+                    ("confidence", frame.C), ("render", render)):
+        arr = np.load(out / (name + ".npy"))
+        assert arr.dtype == np.float32 and arr.shape == tuple(t.shape)
+        np.testing.assert_array_equal(arr, t.float().numpy())
+    # a frame whose render was not kept leaves no render file behind
+    out2 = tmp_path / "dump2"
+    bench.dump_outputs(str(out2), frame, None)
+    assert "render.npy" not in os.listdir(out2)
