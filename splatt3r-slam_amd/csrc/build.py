@@ -69,6 +69,7 @@ SOURCES = {
     "net_ops.hip": STRICT,
     "gn_backend.hip": STRICT,
     "retrieval.hip": STRICT,
+    "ingest.hip": STRICT,
 }
 
 

@@ -7,7 +7,9 @@ the reference's FPS window (main.py:363-535):
                   LANCZOS 640x480 -> 512x384 + centre crop + ImgNorm,
                   splatt3r_utils.py:658-693, frame.py:122-133) -> pinned
                   buffer -> H2D on a copy stream, on worker threads a few
-                  frames ahead of the tracker
+                  frames ahead of the tracker; ingest="device" uploads the
+                  raw uint8 frame instead and does that work in one HIP
+                  launch (splatt3r_amd/ingest.py), with the same result
   RenderWriter    the per-frame render export (main.py:436-446 `gs_init_*`,
                   :490-506 `gs_track_*`): D2H of the rendered [1,1,3,H,W]
                   image into a pinned ring, then uint8 conversion and the
@@ -27,6 +29,7 @@ PIL does the PNG codec work, at cv2's default compression level 1.
 from __future__ import annotations
 
 import concurrent.futures as cf
+import os
 import pathlib
 import queue
 import threading
@@ -97,8 +100,9 @@ def write_synthetic_tum(root, n: int, H: int = 480, W: int = 640, seed: int = 0,
 
 class LoadedFrame:
     """One frame as create_frame needs it: img [1,3,H,W] on the device
-    (ImgNorm), true_shape [[H, W]], the unnormalised uint8 image and the
-    copy-stream event after which `img` is valid."""
+    (ImgNorm), true_shape [[H, W]], the unnormalised uint8 image (a numpy
+    array; with device ingest a device tensor) and the copy-stream event
+    after which `img` is valid."""
 
     __slots__ = ("index", "timestamp", "img", "true_shape", "uimg", "ready")
 
@@ -112,6 +116,8 @@ class LoadedFrame:
         s = stream or torch.cuda.current_stream(self.img.device)
         s.wait_event(self.ready)
         self.img.record_stream(s)
+        if torch.is_tensor(self.uimg) and self.uimg.is_cuda:    # device ingest
+            self.uimg.record_stream(s)
         return self.img
 
 
@@ -122,10 +128,24 @@ class FrameLoader:
     iteration.  `close()` stops the workers."""
 
     def __init__(self, dataset, device, img_size: int = 512, workers: int = 3, depth: int = 6,
-                 start: int = 0, stop: Optional[int] = None):
+                 start: int = 0, stop: Optional[int] = None, ingest: Optional[str] = None):
+        """ingest: "host" (resize_img on the worker, float32 upload) or
+        "device" (the raw uint8 frame is uploaded and ingest.resize_img_device
+        resizes, crops and normalises it on the loader's stream; the same
+        `img`, and `uimg` stays on the device).  None: the environment
+        variable S3_INGEST, default "host"."""
         self.ds = dataset
         self.device = torch.device(device)
         self.img_size = img_size
+        self.ingest = os.environ.get("S3_INGEST", "host") if ingest is None else ingest
+        if self.ingest not in ("host", "device"):
+            raise ValueError(f"FrameLoader: ingest must be 'host' or 'device', got {self.ingest!r}")
+        # device mode: pinned uint8 staging buffers [buffer, event of the
+        # last upload that read it]; a worker takes one, waits for that
+        # event, fills it, and puts it back with its own upload's event
+        self._ring: "queue.Queue" = queue.Queue()
+        for _ in range(workers + 1):
+            self._ring.put([None, None])
         self.stream = torch.cuda.Stream(device=self.device)
         self._pool = cf.ThreadPoolExecutor(max_workers=workers, thread_name_prefix="s3-load")
         self._next = start
@@ -142,7 +162,32 @@ class FrameLoader:
                 break
             self._futs[i] = self._pool.submit(self._load, i)
 
+    def _load_device(self, i) -> LoadedFrame:
+        from splatt3r_amd.ingest import resize_img_device
+        raw = self.ds.read_img(i)                          # uint8 [H, W, 3]
+        slot = self._ring.get()
+        try:
+            buf, busy = slot
+            if busy is not None:
+                busy.synchronize()                         # the upload that last read buf
+            if buf is None or buf.shape != raw.shape:
+                buf = slot[0] = torch.empty(raw.shape, dtype=torch.uint8, pin_memory=True)
+            buf.numpy()[...] = raw
+            with self._lock, torch.cuda.stream(self.stream):
+                dev = buf.to(self.device, non_blocking=True)
+                slot[1] = torch.cuda.Event()
+                slot[1].record(self.stream)
+                r = resize_img_device(dev, self.img_size, stream=self.stream)
+                ev = torch.cuda.Event()
+                ev.record(self.stream)
+        finally:
+            self._ring.put(slot)
+        return LoadedFrame(i, self.ds.timestamps[i], r["img"], torch.tensor(r["true_shape"]),
+                           r["unnormalized_img"], ev)
+
     def _load(self, i) -> LoadedFrame:
+        if self.ingest == "device":
+            return self._load_device(i)
         from splatt3r_amd.splatt3r_utils import resize_img
         t, img = self.ds[i]
         r = resize_img(img, self.img_size)

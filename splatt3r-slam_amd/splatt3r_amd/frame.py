@@ -15,6 +15,7 @@ import threading
 from enum import Enum
 from typing import Optional
 
+import numpy as np
 import torch
 
 import lietorch
@@ -135,13 +136,27 @@ class Frame:
 def create_frame(i, img, T_WC=None, img_size=512, device="cuda:0"):
     """frame.py:122-133.  `img` is either an HxWx3 float array in [0,1]
     (resized by the reference rule, splatt3r_utils.resize_img) or an already
-    normalised [1,3,H,W] tensor (the synthetic bench frames)."""
+    normalised [1,3,H,W] tensor (the synthetic bench frames), or a raw uint8
+    HxWx3 frame as a camera or decoder hands it over: with a CUDA `device`
+    that one is uploaded as it is and resized, cropped and normalised there
+    (ingest.resize_img_device: the same values, and `uimg` on the device)."""
     from splatt3r_amd.splatt3r_utils import resize_img
+    u8 = img.ndim == 3 and img.dtype == (torch.uint8 if torch.is_tensor(img) else np.uint8)
+    if u8 and torch.device(device).type != "cuda":
+        img = img.cpu().numpy() if torch.is_tensor(img) else img
+        img = img.astype(np.float32) / 255.0                 # the dataset's own conversion
+        u8 = False
     if torch.is_tensor(img) and img.dim() == 4:
         rgb = img.to(device)
         H, W = rgb.shape[-2:]
         true_shape = torch.tensor([[H, W]], dtype=torch.int32)
         uimg = None
+    elif u8:
+        from splatt3r_amd import ingest
+        r = ingest.resize_img_device(img, img_size, device=device)
+        rgb = r["img"]
+        true_shape = torch.tensor(r["true_shape"])
+        uimg = ingest.unit_image(r["unnormalized_img"])
     else:
         r = resize_img(img, img_size)
         rgb = r["img"].to(device)

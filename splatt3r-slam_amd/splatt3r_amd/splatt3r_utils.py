@@ -23,6 +23,7 @@ import torch
 
 import lietorch
 from splatt3r_amd import _lib, matching
+from splatt3r_amd import ingest  # noqa: F401  (registers the s3i_* signatures)
 from splatt3r_amd.config import config
 from splatt3r_amd.render import (DecoderSplattingCUDA, camera_settings, camera_settings_sim3,
                                   normalize_intrinsics,
