@@ -460,8 +460,10 @@ int64_t oracle_raster(const oracle_cam* cam, int64_t P, int M, const float* mean
           for (int ch = 0; ch < 3; ++ch)
             dL_dsh[(i * M + k) * 3 + ch] =
                 B[k] * (clamped[i * 3 + ch] ? 0.0f : dL_dcolors[i * 3 + ch]);
-        /* degree-0 has no view-direction term; higher degrees are checked
-           against autograd in tests, not restated here */
+        /* degree-0 has no view-direction term; for higher degrees dL_dmeans3D
+           of the kernels is checked against float64 autograd
+           (tests/test_raster_grad.py
+           test_hip_backward_vs_float64_reference), not restated here */
       }
       dL_dmeans3D[i * 3] = gmx;
       dL_dmeans3D[i * 3 + 1] = gmy;
