@@ -21,6 +21,8 @@
  *   gsr_binning_bytes(R)     -> binning workspace (per tile-instance)
  *   gsr_render(...)          -> out_color [3,H,W]
  *   gsr_backward(...)        -> gradients (optional)
+ * gsr_render_depth / gsr_backward_depth in place of gsr_render /
+ * gsr_backward also give depth and accumulated opacity (below).
  * The three workspaces are opaque and must be kept alive from preprocess to
  * backward (the Python layer stores them as uint8 tensors, like the
  * reference's geomBuffer / binningBuffer / imgBuffer).
@@ -103,6 +105,50 @@ int gsr_backward(const gsr_settings* s, int64_t P, int M, int64_t num_rendered,
                  float* dL_dconic, float* dL_dopacity, float* dL_dcolors,
                  float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
                  float* dL_dscales, float* dL_drotations, void* stream);
+
+/* Depth and accumulated opacity from the blend pass (DESIGN.md "Rasterizer:
+ * depth and alpha").  Per pixel, with the colour blend's own alpha_i, T_i,
+ * skip rules and stop rule:
+ *   depth = sum z_i alpha_i T_i     alpha = sum alpha_i T_i
+ * accumulated left to right like the colour channels, no background term.
+ * z_i is the Gaussian's view-space z (the value of the near-plane cull and
+ * the depth sort), in the units of means3D.
+ *
+ * gsr_render_depth: called after gsr_preprocess in place of gsr_render.
+ * out_color is bit-identical to gsr_render's; out_depth / out_alpha are
+ * [H,W]; view_z [P] is filled for every Gaussian, culled ones included
+ * (the backward's saved tensor).  P == 0: out_color is the background,
+ * depth and alpha are zero. */
+int gsr_render_depth(const gsr_settings* s, int64_t P, int64_t num_rendered,
+                     const int32_t* radii, void* geom, void* binning, void* image,
+                     const float* means3D, float* out_color, float* out_depth,
+                     float* out_alpha, float* view_z, void* stream);
+
+/* gsr_forward_deferred plus out_depth, out_alpha, view_z.  Same info
+ * contract: a non-zero status invalidates all three images. */
+int gsr_forward_deferred_depth(const gsr_settings* s, int64_t P, int M, const float* means3D,
+                               const float* scales, const float* rotations,
+                               const float* cov3D_precomp, const float* shs,
+                               const float* colors_precomp, const float* opacities,
+                               int32_t* radii, void* geom, void* binning, int64_t capacity,
+                               int key_bits, void* image, float* out_color, float* out_depth,
+                               float* out_alpha, float* view_z, int64_t* info, void* stream);
+
+/* gsr_backward for a forward by gsr_render_depth: dL_dout_depth and
+ * dL_dout_alpha [H,W] may each be NULL (zero).  dL_dz [P] is scratch (the
+ * gradient of the loss by each Gaussian's view z; zeroed here like
+ * dL_dconic); its chain to the mean, dL_dz_i (vm[2], vm[6], vm[10]), is added
+ * to dL_dmeans3D. */
+int gsr_backward_depth(const gsr_settings* s, int64_t P, int M, int64_t num_rendered,
+                       const float* means3D, const float* scales, const float* rotations,
+                       const float* cov3D_precomp, const float* shs,
+                       const float* colors_precomp, const float* opacities,
+                       const int32_t* radii, const void* geom, const void* binning,
+                       const void* image, const float* view_z, const float* dL_dout_color,
+                       const float* dL_dout_depth, const float* dL_dout_alpha,
+                       float* dL_dmeans2D, float* dL_dconic, float* dL_dopacity,
+                       float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
+                       float* dL_dscales, float* dL_drotations, float* dL_dz, void* stream);
 
 /* GaussianRasterizer.markVisible: present[i] = (view z > 0.2). */
 int gsr_mark_visible(int64_t P, const float* means3D, const float* viewmatrix,

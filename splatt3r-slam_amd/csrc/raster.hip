@@ -13,6 +13,10 @@
 //           reduced across the wave with DPP/shuffles before one lane issues
 //           the global atomics (64x fewer atomics than one per pixel), then a
 //           per-Gaussian pass for the EWA / projection / SH chain rule.
+// Depth:    gsr_render_depth / gsr_backward_depth: the blend's depth variant
+//           also accumulates sum z alpha T and sum alpha T per pixel (z = view
+//           z, k_view_z), the backward's carries the two extra channels and
+//           dL/dz per Gaussian.  The colour instantiations are unchanged.
 // Tile blocks are remapped so that each XCD (private L2) receives a
 // contiguous band of tiles: neighbouring tiles share most of their splats.
 #include <algorithm>
@@ -1344,14 +1348,33 @@ k_tile_sort(int ntiles, const uint2* __restrict__ ranges, uint32_t* __restrict__
 }
 
 // --------------------------------------------------------------- blend ----
+// View-space z of every Gaussian, culled ones included: the expression of
+// preprocess_one's near-plane cull and depth key (depth variant only; the
+// geometry workspace keeps its layout, view_z is the caller's buffer).
+__global__ void __launch_bounds__(kThreads)
+k_view_z(int64_t P, const float* __restrict__ means, const float* __restrict__ vm,
+         float* __restrict__ view_z) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= P) return;
+  float pv[3];
+  xform43(vm, means[i * 3 + 0], means[i * 3 + 1], means[i * 3 + 2], pv);
+  view_z[i] = pv[2];
+}
+
+// DEPTH: two more accumulators with the colour channels' alpha_i T_i weights,
+// depth = sum z_i alpha_i T_i and alpha = sum alpha_i T_i (no background
+// term), z staged beside the records.  DEPTH = false is the colour blend.
+template <bool DEPTH>
 __global__ void __launch_bounds__(BS)
 k_blend(int W, int H, int gx, int ntiles, const uint2* __restrict__ ranges,
         const uint32_t* __restrict__ point_list, GeomState g, const float* __restrict__ bg,
         float* __restrict__ final_T, uint32_t* __restrict__ n_contrib,
-        float* __restrict__ out) {
+        float* __restrict__ out, const float* __restrict__ view_z,
+        float* __restrict__ out_depth, float* __restrict__ out_alpha) {
   __shared__ float4 s_r0[BS];
   __shared__ float4 s_r1[BS];  // (conic.c, opacity, r, g)
   __shared__ float s_b[BS];
+  __shared__ float s_z[DEPTH ? BS : 1];
   const int tile = xcd_tile(blockIdx.x, ntiles);
   const int tx = tile % gx, ty = tile / gx;
   const int lx = threadIdx.x % BX, ly = threadIdx.x / BX;
@@ -1365,6 +1388,7 @@ k_blend(int W, int H, int gx, int ntiles, const uint2* __restrict__ ranges,
   float T = 1.0f;
   uint32_t contributor = 0, last_contributor = 0;
   float C0 = 0.f, C1 = 0.f, C2 = 0.f;
+  float Dz = 0.f, A = 0.f;
   int todo = todo_total;
   for (int rd = 0; rd < rounds; ++rd, todo -= BS) {
     if (__syncthreads_count(done) == BS) break;
@@ -1374,6 +1398,7 @@ k_blend(int W, int H, int gx, int ntiles, const uint2* __restrict__ ranges,
       s_r0[threadIdx.x] = g.rec0[id];
       s_r1[threadIdx.x] = g.rec1[id];
       s_b[threadIdx.x] = g.blue[id];
+      if constexpr (DEPTH) s_z[threadIdx.x] = view_z[id];
     }
     __syncthreads();
     const int n = todo < BS ? todo : BS;
@@ -1395,6 +1420,10 @@ k_blend(int W, int H, int gx, int ntiles, const uint2* __restrict__ ranges,
       C0 = C0 + b.z * alpha * T;
       C1 = C1 + b.w * alpha * T;
       C2 = C2 + s_b[j] * alpha * T;
+      if constexpr (DEPTH) {
+        Dz = Dz + s_z[j] * alpha * T;
+        A = A + alpha * T;
+      }
       T = test_T;
       last_contributor = contributor;
     }
@@ -1406,6 +1435,10 @@ k_blend(int W, int H, int gx, int ntiles, const uint2* __restrict__ ranges,
     out[pid] = C0 + T * bg[0];
     out[H * W + pid] = C1 + T * bg[1];
     out[2 * H * W + pid] = C2 + T * bg[2];
+    if constexpr (DEPTH) {
+      out_depth[pid] = Dz;
+      out_alpha[pid] = A;
+    }
   }
 }
 
@@ -1466,21 +1499,30 @@ __device__ __forceinline__ float wave_sum8_t(const float (&v)[8], int lane) {
 // conic x/y/w, opacity, colour r/g/b.
 constexpr int kGS = 9;
 
+// DEPTH: five feature channels (r, g, b, z, 1) with pixel gradients (dC0,
+// dC1, dC2, dD, dA); dL_ddepth / dL_dalpha_img may be null (zero).  A tenth
+// slot accumulates dL/dz_i = sum alpha_i T_i dD.  DEPTH = false is the
+// colour backward.
+template <bool DEPTH>
 __global__ void __launch_bounds__(BS)
 k_blend_backward(int W, int H, int gx, int ntiles, const uint2* __restrict__ ranges,
                  const uint32_t* __restrict__ point_list, GeomState g,
                  const float* __restrict__ bg, const float* __restrict__ final_Ts,
                  const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix,
                  float* __restrict__ dL_dmean2D, float* __restrict__ dL_dconic,
-                 float* __restrict__ dL_dopacity, float* __restrict__ dL_dcolors) {
+                 float* __restrict__ dL_dopacity, float* __restrict__ dL_dcolors,
+                 const float* __restrict__ view_z, const float* __restrict__ dL_ddepth,
+                 const float* __restrict__ dL_dalpha_img, float* __restrict__ dL_dz) {
+  constexpr int GS = DEPTH ? kGS + 1 : kGS;
   __shared__ float4 s_r0[BS];
   __shared__ float4 s_r1[BS];
   __shared__ float s_b[BS];
+  __shared__ float s_z[DEPTH ? BS : 1];
   __shared__ uint32_t s_id[BS];
   // per-batch block sums: the 4 waves' reduced gradients meet in LDS and
   // each (Gaussian, tile) pair issues its 9 global atomics once, from the
   // lane that owns the Gaussian, instead of once per wave from lane 0
-  __shared__ float s_acc[BS * kGS];
+  __shared__ float s_acc[BS * GS];
   __shared__ int s_hit[BS];
   const int tile = xcd_tile(blockIdx.x, ntiles);
   const int tx = tile % gx, ty = tile / gx;
@@ -1520,6 +1562,12 @@ k_blend_backward(int W, int H, int gx, int ntiles, const uint2* __restrict__ ran
   const float bg_dot = bg[0] * dpix0 + bg[1] * dpix1 + bg[2] * dpix2;
   float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f;
   float last_alpha = 0.f, lc0 = 0.f, lc1 = 0.f, lc2 = 0.f;
+  // depth variant: the z and constant-1 channels (no background term)
+  float dpixd = 0.f, dpixa = 0.f, accz = 0.f, acca = 0.f, lz = 0.f;
+  if constexpr (DEPTH) {
+    if (inside && dL_ddepth) dpixd = dL_ddepth[pid];
+    if (inside && dL_dalpha_img) dpixa = dL_dalpha_img[pid];
+  }
   const float ddelx_dx = 0.5f * W, ddely_dy = 0.5f * H;
   const int vslot = ((lane >> 5) & 1) * 4 + ((lane >> 4) & 1) * 2 + ((lane >> 3) & 1);
   int todo = todo_total;
@@ -1528,7 +1576,7 @@ k_blend_backward(int W, int H, int gx, int ntiles, const uint2* __restrict__ ran
     const int t = threadIdx.x;
     if (t < n && s_hit[t]) {
       const uint32_t id = s_id[t];
-      const float* a = s_acc + t * kGS;
+      const float* a = s_acc + t * GS;
       atomicAdd(&dL_dmean2D[id * 3 + 0], a[0]);
       atomicAdd(&dL_dmean2D[id * 3 + 1], a[1]);
       atomicAdd(&dL_dconic[id * 4 + 0], a[2]);
@@ -1538,6 +1586,7 @@ k_blend_backward(int W, int H, int gx, int ntiles, const uint2* __restrict__ ran
       atomicAdd(&dL_dcolors[id * 3 + 0], a[6]);
       atomicAdd(&dL_dcolors[id * 3 + 1], a[7]);
       atomicAdd(&dL_dcolors[id * 3 + 2], a[8]);
+      if constexpr (DEPTH) atomicAdd(&dL_dz[id], a[9]);
     }
   };
   for (int rd = 0; rd < rounds; ++rd, todo -= BS) {
@@ -1551,9 +1600,10 @@ k_blend_backward(int W, int H, int gx, int ntiles, const uint2* __restrict__ ran
       s_r0[threadIdx.x] = g.rec0[id];
       s_r1[threadIdx.x] = g.rec1[id];
       s_b[threadIdx.x] = g.blue[id];
+      if constexpr (DEPTH) s_z[threadIdx.x] = view_z[id];
     }
 #pragma unroll
-    for (int k = 0; k < kGS; ++k) s_acc[threadIdx.x * kGS + k] = 0.f;
+    for (int k = 0; k < GS; ++k) s_acc[threadIdx.x * GS + k] = 0.f;
     s_hit[threadIdx.x] = 0;
     __syncthreads();
     const int n = todo < BS ? todo : BS;
@@ -1570,7 +1620,7 @@ k_blend_backward(int W, int H, int gx, int ntiles, const uint2* __restrict__ ran
       ok = ok && !(alpha < 1.0f / 255.0f);
       if (!__any(ok)) continue;
       float gv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      float gb = 0.f;
+      float gb = 0.f, gz = 0.f;
       if (ok) {
         T = T / (1.0f - alpha);
         const float dchannel_dcolor = alpha * T;
@@ -1583,6 +1633,14 @@ k_blend_backward(int W, int H, int gx, int ntiles, const uint2* __restrict__ ran
         gv[6] = dchannel_dcolor * dpix0;
         gv[7] = dchannel_dcolor * dpix1;
         gb = dchannel_dcolor * dpix2;
+        if constexpr (DEPTH) {
+          const float z = s_z[j];
+          accz = last_alpha * lz + (1.0f - last_alpha) * accz;
+          acca = last_alpha + (1.0f - last_alpha) * acca;
+          lz = z;
+          dL_dalpha = dL_dalpha + (z - accz) * dpixd + (1.0f - acca) * dpixa;
+          gz = dchannel_dcolor * dpixd;
+        }
         dL_dalpha = dL_dalpha * T;
         last_alpha = alpha;
         dL_dalpha = dL_dalpha + (-T_final / (1.0f - alpha)) * bg_dot;
@@ -1599,9 +1657,11 @@ k_blend_backward(int W, int H, int gx, int ntiles, const uint2* __restrict__ ran
       }
       const float r8 = wave_sum8_t(gv, lane);
       gb = wave_sum(gb);
-      if ((lane & 7) == 0) atomicAdd(&s_acc[j * kGS + vslot], r8);
+      if constexpr (DEPTH) gz = wave_sum(gz);
+      if ((lane & 7) == 0) atomicAdd(&s_acc[j * GS + vslot], r8);
       if (lane == 0) {
-        atomicAdd(&s_acc[j * kGS + 8], gb);
+        atomicAdd(&s_acc[j * GS + 8], gb);
+        if constexpr (DEPTH) atomicAdd(&s_acc[j * GS + 9], gz);
         s_hit[j] = 1;
       }
     }
@@ -1623,7 +1683,7 @@ k_preprocess_backward(int64_t P, Cam cam, const float* __restrict__ means,
                       const float* __restrict__ dL_dconic, const float* __restrict__ dL_dcolor,
                       float* __restrict__ dL_dmeans, float* __restrict__ dL_dcov,
                       float* __restrict__ dL_dsh, float* __restrict__ dL_dscale,
-                      float* __restrict__ dL_drot) {
+                      float* __restrict__ dL_drot, const float* __restrict__ dL_dz) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= P) return;
   if (!(radii[i] > 0)) {
@@ -1735,6 +1795,13 @@ k_preprocess_backward(int64_t P, Cam cam, const float* __restrict__ means,
     gmx = gmx + ((s2 - ox * ox) * ddx - oy * ox * ddy - oz * ox * ddz) * inv32;
     gmy = gmy + (-ox * oy * ddx + (s2 - oy * oy) * ddy - oz * oy * ddz) * inv32;
     gmz = gmz + (-ox * oz * ddx - oy * oz * ddy + (s2 - oz * oz) * ddz) * inv32;
+  }
+  if (dL_dz) {
+    // rendered depth -> view z -> world mean (view z = row 2 of xform43)
+    const float dz = dL_dz[i];
+    gmx = gmx + dz * vm[2];
+    gmy = gmy + dz * vm[6];
+    gmz = gmz + dz * vm[10];
   }
   dL_dmeans[i * 3 + 0] = gmx;
   dL_dmeans[i * 3 + 1] = gmy;
@@ -1937,14 +2004,38 @@ namespace {
 // capacity in the sync-free forward).  kmin / span / bits: the depth sort's
 // key range and pass width.  dyn (sync-free): device {kmin, span, instances}
 // that override kmin / span and bound the instance passes.
+// Depth variant (dz.out_depth != nullptr): view_z is filled from means3D for
+// every Gaussian and the blend also writes depth and accumulated opacity.
+struct DepthOut {
+  const float* means3D = nullptr;
+  float* out_depth = nullptr;
+  float* out_alpha = nullptr;
+  float* view_z = nullptr;
+};
+
 int render_impl(const gsr_settings* s, int64_t P, int64_t R, void* geom, void* binning,
                 void* image, float* out_color, hipStream_t st, uint32_t kmin, uint32_t span,
-                int bits, const uint32_t* dyn) {
+                int bits, const uint32_t* dyn, DepthOut dz = DepthOut{}) {
   const int W = s->image_width, H = s->image_height;
   const int gx = (W + BX - 1) / BX, gy = (H + BY - 1) / BY, ntiles = gx * gy;
+  if (P == 0 && dz.out_depth) {
+    // empty tile lists: colour = background, depth = alpha = 0, T = 1
+    ImageState im = carve_image(image, H, W);
+    S3_HIP(hipMemsetAsync(im.ranges, 0, sizeof(uint2) * ntiles, st));
+    k_blend<true><<<ntiles, BS, 0, st>>>(W, H, gx, ntiles, im.ranges, nullptr, GeomState{}, s->bg,
+                                         im.final_T, im.n_contrib, out_color, dz.view_z,
+                                         dz.out_depth, dz.out_alpha);
+    S3_LAUNCH_CHECK();
+    return S3_OK;
+  }
   if (P == 0) {
     S3_HIP(hipMemsetAsync(out_color, 0, sizeof(float) * 3 * (size_t)H * W, st));
     return S3_OK;
+  }
+  if (dz.out_depth) {
+    k_view_z<<<(unsigned)s3::cdiv(P, kThreads), kThreads, 0, st>>>(P, dz.means3D, s->viewmatrix,
+                                                                   dz.view_z);
+    S3_LAUNCH_CHECK();
   }
   GeomState g = carve_geom(geom, P);
   BinningState b = carve_binning(binning, R);
@@ -2016,21 +2107,21 @@ int render_impl(const gsr_settings* s, int64_t P, int64_t R, void* geom, void* b
     tmark(4, st);
   }
   tmark(5, st);
-  k_blend<<<ntiles, BS, 0, st>>>(W, H, gx, ntiles, im.ranges, point_list, g, s->bg, im.final_T,
-                                 im.n_contrib, out_color);
+  if (dz.out_depth)
+    k_blend<true><<<ntiles, BS, 0, st>>>(W, H, gx, ntiles, im.ranges, point_list, g, s->bg,
+                                         im.final_T, im.n_contrib, out_color, dz.view_z,
+                                         dz.out_depth, dz.out_alpha);
+  else
+    k_blend<false><<<ntiles, BS, 0, st>>>(W, H, gx, ntiles, im.ranges, point_list, g, s->bg,
+                                          im.final_T, im.n_contrib, out_color, nullptr, nullptr,
+                                          nullptr);
   S3_LAUNCH_CHECK();
   tmark(6, st);
   return S3_OK;
 }
-}  // namespace
 
-extern "C" {
-
-int gsr_render(const gsr_settings* s, int64_t P, int64_t R, const int32_t* radii,
-               void* geom, void* binning, void* image, float* out_color, void* stream) {
-  S3_REQUIRE(s && P >= 0 && R >= 0, "gsr_render: bad arguments");
-  S3_REQUIRE(R < ((int64_t)1 << 32), "gsr_render: too many tile instances");
-  (void)radii;
+int render_two_call(const gsr_settings* s, int64_t P, int64_t R, void* geom, void* binning,
+                    void* image, float* out_color, void* stream, DepthOut dz) {
   // the depth-key range of this geometry buffer, from gsr_preprocess's
   // read-back (full 32-bit width if the buffer was filled elsewhere)
   uint32_t kmin = 0, kmax = 0xFFFFFFFEu;
@@ -2041,15 +2132,15 @@ int gsr_render(const gsr_settings* s, int64_t P, int64_t R, const int32_t* radii
   // visible keys map to [0, kmax - kmin], culled ones (~0u) to span
   const uint32_t span = kmax - kmin + 1u;
   return render_impl(s, P, R, geom, binning, image, out_color, s3::as_stream(stream), kmin, span,
-                     bit_length(span), nullptr);
+                     bit_length(span), nullptr, dz);
 }
 
-int gsr_forward_deferred(const gsr_settings* s, int64_t P, int M, const float* means3D,
-                         const float* scales, const float* rotations, const float* cov3D_precomp,
-                         const float* shs, const float* colors_precomp, const float* opacities,
-                         int32_t* radii, void* geom, void* binning, int64_t capacity,
-                         int key_bits, void* image, float* out_color, int64_t* info,
-                         void* stream) {
+int forward_deferred_impl(const gsr_settings* s, int64_t P, int M, const float* means3D,
+                          const float* scales, const float* rotations,
+                          const float* cov3D_precomp, const float* shs,
+                          const float* colors_precomp, const float* opacities, int32_t* radii,
+                          void* geom, void* binning, int64_t capacity, int key_bits, void* image,
+                          float* out_color, int64_t* info, void* stream, DepthOut dz) {
   S3_REQUIRE(s && info && P >= 0, "gsr_forward_deferred: bad arguments");
   S3_REQUIRE(P < (int64_t)1 << 31, "gsr_forward_deferred: P too large");
   S3_REQUIRE(capacity >= 1 && capacity < ((int64_t)1 << 32) && key_bits >= 1 && key_bits <= 32,
@@ -2064,7 +2155,7 @@ int gsr_forward_deferred(const gsr_settings* s, int64_t P, int M, const float* m
   hipStream_t st = s3::as_stream(stream);
   if (P == 0) {
     S3_HIP(hipMemsetAsync(info, 0, 3 * sizeof(int64_t), st));
-    return render_impl(s, 0, 0, geom, binning, image, out_color, st, 0, 1, 1, nullptr);
+    return render_impl(s, 0, 0, geom, binning, image, out_color, st, 0, 1, 1, nullptr, dz);
   }
   Cam cam = make_cam(s, M);
   GeomState g = carve_geom(geom, P);
@@ -2080,7 +2171,117 @@ int gsr_forward_deferred(const gsr_settings* s, int64_t P, int M, const float* m
   tmark(2, st);
   const uint32_t span_bound = key_bits >= 32 ? 0xFFFFFFFFu : ((1u << key_bits) - 1u);
   return render_impl(s, P, capacity, geom, binning, image, out_color, st, 0u, span_bound,
-                     key_bits, g.dyn);
+                     key_bits, g.dyn, dz);
+}
+
+// depth variant of the backward: view_z != nullptr
+struct DepthGrad {
+  const float* view_z = nullptr;
+  const float* dL_dout_depth = nullptr;  // may be null: zero
+  const float* dL_dout_alpha = nullptr;  // may be null: zero
+  float* dL_dz = nullptr;                // [P] scratch, zeroed here
+};
+
+int backward_impl(const gsr_settings* s, int64_t P, int M, int64_t R, const float* means3D,
+                  const float* scales, const float* rotations, const float* cov3D_precomp,
+                  const float* shs, const int32_t* radii, const void* geom, const void* binning,
+                  const void* image, const float* dL_dout, float* dL_dmeans2D, float* dL_dconic,
+                  float* dL_dopacity, float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D,
+                  float* dL_dsh, float* dL_dscales, float* dL_drotations, void* stream,
+                  DepthGrad dg) {
+  hipStream_t st = s3::as_stream(stream);
+  // the accumulated gradient outputs start at zero: one launch for all
+  ZeroList zl{};
+  auto add = [&](float* p, int64_t n) {
+    if (p && n > 0) { zl.p[zl.cnt] = p; zl.n[zl.cnt] = n; ++zl.cnt; }
+  };
+  // (only the blend's atomic accumulators: k_preprocess_backward writes
+  // every element of the per-Gaussian outputs, zeros for culled ones)
+  add(dL_dmeans2D, P * 3);
+  add(dL_dconic, P * 4);
+  add(dL_dopacity, P);
+  add(dL_dcolors, P * 3);
+  add(dg.dL_dz, P);
+  if (zl.cnt > 0) {
+    int64_t nmax = 0;
+    for (int k = 0; k < zl.cnt; ++k) nmax = zl.n[k] > nmax ? zl.n[k] : nmax;
+    k_zero_multi<<<dim3((unsigned)s3::cdiv(nmax, kThreads * 4), zl.cnt), kThreads, 0, st>>>(zl);
+    S3_LAUNCH_CHECK();
+  }
+  if (P == 0) return S3_OK;
+  const int W = s->image_width, H = s->image_height;
+  const int gx = (W + BX - 1) / BX, gy = (H + BY - 1) / BY, ntiles = gx * gy;
+  GeomState g = carve_geom(const_cast<void*>(geom), P);
+  BinningState b = carve_binning(const_cast<void*>(binning), R);
+  ImageState im = carve_image(const_cast<void*>(image), H, W);
+  const uint32_t* point_list = b.vals[R > 0 ? tile_sort_buffer(ntiles) : 0];
+  if (dg.view_z)
+    k_blend_backward<true><<<ntiles, BS, 0, st>>>(
+        W, H, gx, ntiles, im.ranges, point_list, g, s->bg, im.final_T, im.n_contrib, dL_dout,
+        dL_dmeans2D, dL_dconic, dL_dopacity, dL_dcolors, dg.view_z, dg.dL_dout_depth,
+        dg.dL_dout_alpha, dg.dL_dz);
+  else
+    k_blend_backward<false><<<ntiles, BS, 0, st>>>(
+        W, H, gx, ntiles, im.ranges, point_list, g, s->bg, im.final_T, im.n_contrib, dL_dout,
+        dL_dmeans2D, dL_dconic, dL_dopacity, dL_dcolors, nullptr, nullptr, nullptr, nullptr);
+  S3_LAUNCH_CHECK();
+  Cam cam = make_cam(s, M);
+  k_preprocess_backward<<<(unsigned)s3::cdiv(P, kThreads), kThreads, 0, st>>>(
+      P, cam, means3D, scales, rotations, cov3D_precomp, shs, radii, g, s->viewmatrix,
+      s->projmatrix, s->campos, dL_dmeans2D, dL_dconic, dL_dcolors, dL_dmeans3D, dL_dcov3D,
+      dL_dsh, dL_dscales, dL_drotations, dg.dL_dz);
+  S3_LAUNCH_CHECK();
+  return S3_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int gsr_render(const gsr_settings* s, int64_t P, int64_t R, const int32_t* radii,
+               void* geom, void* binning, void* image, float* out_color, void* stream) {
+  S3_REQUIRE(s && P >= 0 && R >= 0, "gsr_render: bad arguments");
+  S3_REQUIRE(R < ((int64_t)1 << 32), "gsr_render: too many tile instances");
+  (void)radii;
+  return render_two_call(s, P, R, geom, binning, image, out_color, stream, DepthOut{});
+}
+
+int gsr_render_depth(const gsr_settings* s, int64_t P, int64_t R, const int32_t* radii,
+                     void* geom, void* binning, void* image, const float* means3D,
+                     float* out_color, float* out_depth, float* out_alpha, float* view_z,
+                     void* stream) {
+  S3_REQUIRE(s && P >= 0 && R >= 0, "gsr_render_depth: bad arguments");
+  S3_REQUIRE(R < ((int64_t)1 << 32), "gsr_render_depth: too many tile instances");
+  S3_REQUIRE(out_depth && out_alpha && (P == 0 || (means3D && view_z)),
+             "gsr_render_depth: out_depth, out_alpha, means3D and view_z are required");
+  (void)radii;
+  return render_two_call(s, P, R, geom, binning, image, out_color, stream,
+                         DepthOut{means3D, out_depth, out_alpha, view_z});
+}
+
+int gsr_forward_deferred(const gsr_settings* s, int64_t P, int M, const float* means3D,
+                         const float* scales, const float* rotations, const float* cov3D_precomp,
+                         const float* shs, const float* colors_precomp, const float* opacities,
+                         int32_t* radii, void* geom, void* binning, int64_t capacity,
+                         int key_bits, void* image, float* out_color, int64_t* info,
+                         void* stream) {
+  return forward_deferred_impl(s, P, M, means3D, scales, rotations, cov3D_precomp, shs,
+                               colors_precomp, opacities, radii, geom, binning, capacity,
+                               key_bits, image, out_color, info, stream, DepthOut{});
+}
+
+int gsr_forward_deferred_depth(const gsr_settings* s, int64_t P, int M, const float* means3D,
+                               const float* scales, const float* rotations,
+                               const float* cov3D_precomp, const float* shs,
+                               const float* colors_precomp, const float* opacities,
+                               int32_t* radii, void* geom, void* binning, int64_t capacity,
+                               int key_bits, void* image, float* out_color, float* out_depth,
+                               float* out_alpha, float* view_z, int64_t* info, void* stream) {
+  S3_REQUIRE(out_depth && out_alpha && (P <= 0 || view_z),
+             "gsr_forward_deferred_depth: out_depth, out_alpha and view_z are required");
+  return forward_deferred_impl(s, P, M, means3D, scales, rotations, cov3D_precomp, shs,
+                               colors_precomp, opacities, radii, geom, binning, capacity,
+                               key_bits, image, out_color, info, stream,
+                               DepthOut{means3D, out_depth, out_alpha, view_z});
 }
 
 int gsr_backward(const gsr_settings* s, int64_t P, int M, int64_t R, const float* means3D,
@@ -2094,42 +2295,29 @@ int gsr_backward(const gsr_settings* s, int64_t P, int M, int64_t R, const float
   S3_REQUIRE(s && P >= 0 && R >= 0, "gsr_backward: bad arguments");
   (void)colors_precomp;
   (void)opacities;
-  hipStream_t st = s3::as_stream(stream);
-  // the accumulated gradient outputs start at zero: one launch for all
-  ZeroList zl{};
-  auto add = [&](float* p, int64_t n) {
-    if (p && n > 0) { zl.p[zl.cnt] = p; zl.n[zl.cnt] = n; ++zl.cnt; }
-  };
-  // (only the blend's atomic accumulators: k_preprocess_backward writes
-  // every element of the per-Gaussian outputs, zeros for culled ones)
-  add(dL_dmeans2D, P * 3);
-  add(dL_dconic, P * 4);
-  add(dL_dopacity, P);
-  add(dL_dcolors, P * 3);
-  if (zl.cnt > 0) {
-    int64_t nmax = 0;
-    for (int k = 0; k < zl.cnt; ++k) nmax = zl.n[k] > nmax ? zl.n[k] : nmax;
-    k_zero_multi<<<dim3((unsigned)s3::cdiv(nmax, kThreads * 4), zl.cnt), kThreads, 0, st>>>(zl);
-    S3_LAUNCH_CHECK();
-  }
-  if (P == 0) return S3_OK;
-  const int W = s->image_width, H = s->image_height;
-  const int gx = (W + BX - 1) / BX, gy = (H + BY - 1) / BY, ntiles = gx * gy;
-  GeomState g = carve_geom(const_cast<void*>(geom), P);
-  BinningState b = carve_binning(const_cast<void*>(binning), R);
-  ImageState im = carve_image(const_cast<void*>(image), H, W);
-  k_blend_backward<<<ntiles, BS, 0, st>>>(W, H, gx, ntiles, im.ranges,
-                                          b.vals[R > 0 ? tile_sort_buffer(ntiles) : 0], g, s->bg,
-                                          im.final_T, im.n_contrib, dL_dout, dL_dmeans2D,
-                                          dL_dconic, dL_dopacity, dL_dcolors);
-  S3_LAUNCH_CHECK();
-  Cam cam = make_cam(s, M);
-  k_preprocess_backward<<<(unsigned)s3::cdiv(P, kThreads), kThreads, 0, st>>>(
-      P, cam, means3D, scales, rotations, cov3D_precomp, shs, radii, g, s->viewmatrix,
-      s->projmatrix, s->campos, dL_dmeans2D, dL_dconic, dL_dcolors, dL_dmeans3D, dL_dcov3D,
-      dL_dsh, dL_dscales, dL_drotations);
-  S3_LAUNCH_CHECK();
-  return S3_OK;
+  return backward_impl(s, P, M, R, means3D, scales, rotations, cov3D_precomp, shs, radii, geom,
+                       binning, image, dL_dout, dL_dmeans2D, dL_dconic, dL_dopacity, dL_dcolors,
+                       dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, stream,
+                       DepthGrad{});
+}
+
+int gsr_backward_depth(const gsr_settings* s, int64_t P, int M, int64_t R, const float* means3D,
+                       const float* scales, const float* rotations, const float* cov3D_precomp,
+                       const float* shs, const float* colors_precomp, const float* opacities,
+                       const int32_t* radii, const void* geom, const void* binning,
+                       const void* image, const float* view_z, const float* dL_dout_color,
+                       const float* dL_dout_depth, const float* dL_dout_alpha,
+                       float* dL_dmeans2D, float* dL_dconic, float* dL_dopacity,
+                       float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
+                       float* dL_dscales, float* dL_drotations, float* dL_dz, void* stream) {
+  S3_REQUIRE(s && P >= 0 && R >= 0, "gsr_backward_depth: bad arguments");
+  S3_REQUIRE(P == 0 || (view_z && dL_dz), "gsr_backward_depth: view_z and dL_dz are required");
+  (void)colors_precomp;
+  (void)opacities;
+  return backward_impl(s, P, M, R, means3D, scales, rotations, cov3D_precomp, shs, radii, geom,
+                       binning, image, dL_dout_color, dL_dmeans2D, dL_dconic, dL_dopacity,
+                       dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
+                       stream, DepthGrad{view_z, dL_dout_depth, dL_dout_alpha, dL_dz});
 }
 
 int gsr_mark_visible(int64_t P, const float* means3D, const float* viewmatrix,

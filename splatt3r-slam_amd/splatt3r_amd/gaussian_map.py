@@ -171,10 +171,13 @@ def gl_to_cv_T_WC(T_CW_gl: np.ndarray) -> np.ndarray:
 @torch.inference_mode()
 def render_map(gmap: SharedGaussians, T_WC_cv: np.ndarray, render_w: int, render_h: int,
                vfov_deg: float, bg=VIZ_BG, n: Optional[int] = None, clamp: bool = True,
-               camera=None):
+               camera=None, return_depth=False):
     """Full-map render (visualization.py:467-600): every Gaussian of the map
     rasterized with colors_precomp from an OpenCV camera-to-world pose.
-    Returns the [3, H, W] image (clamped to [0, 1] like the viz when clamp).
+    Returns the [3, H, W] image (clamped to [0, 1] like the viz when clamp);
+    with return_depth, (image, depth [H, W], alpha [H, W]) from the same
+    blend pass: depth = sum z_i alpha_i T_i in world units, alpha =
+    sum alpha_i T_i (neither is clamped).
     `camera`: a precomputed viz_camera tuple (the host camera math is torch
     CPU code whose last bit depends on the host's vector ISA)."""
     from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
@@ -195,8 +198,12 @@ def render_map(gmap: SharedGaussians, T_WC_cv: np.ndarray, render_w: int, render
         bg=torch.tensor(bg, dtype=torch.float32, device=dev), scale_modifier=1.0,
         viewmatrix=view_t.to(dev), projmatrix=full_proj.to(dev), sh_degree=0,
         campos=campos.to(dev), prefiltered=False, debug=False)
-    image, _ = GaussianRasterizer(st)(means3D=sc_means, means2D=torch.zeros_like(sc_means),
-                                      shs=None, colors_precomp=gmap.colors[:n],
-                                      opacities=gmap.opacities[:n, None],
-                                      cov3D_precomp=sc_cov)
-    return image.clamp(0, 1) if clamp else image
+    out = GaussianRasterizer(st)(means3D=sc_means, means2D=torch.zeros_like(sc_means),
+                                 shs=None, colors_precomp=gmap.colors[:n],
+                                 opacities=gmap.opacities[:n, None],
+                                 cov3D_precomp=sc_cov, return_depth=return_depth)
+    image = out[0].clamp(0, 1) if clamp else out[0]
+    if return_depth:
+        # the rasterizer ran on means * s: depth back in world units
+        return image, out[2] / float(s), out[3]
+    return image

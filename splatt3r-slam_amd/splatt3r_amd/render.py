@@ -160,8 +160,13 @@ def camera_settings_sim3(T_context, T_target, K, image_shape, background_color, 
 
 def render_cuda(extrinsics, intrinsics, near, far, image_shape, background_color,
                 gaussian_means, gaussian_covariances, gaussian_sh_coefficients,
-                gaussian_opacities, scale_invariant=True, use_sh=True):
-    """Same contract as cuda_splatting.render_cuda: [b,3,h,w]."""
+                gaussian_opacities, scale_invariant=True, use_sh=True, return_depth=False):
+    """Same contract as cuda_splatting.render_cuda: [b,3,h,w].
+
+    return_depth (extension): (images, depth [b,h,w], alpha [b,h,w]) from the
+    same blend pass: depth = sum z_i alpha_i T_i (view-space z, in the units
+    of gaussian_means: divided by the scale-invariant factor when
+    scale_invariant) and alpha = sum alpha_i T_i."""
     assert use_sh or gaussian_sh_coefficients.shape[-1] == 1
     _, _, _, n = gaussian_sh_coefficients.shape
     degree = isqrt(n) - 1
@@ -172,16 +177,24 @@ def render_cuda(extrinsics, intrinsics, near, far, image_shape, background_color
         gaussian_means = gaussian_means * scale[:, None, None]
     shs = gaussian_sh_coefficients.permute(0, 1, 3, 2).contiguous()
     row, col = torch.triu_indices(3, 3)
-    images = []
+    images, depths, alphas = [], [], []
     for i, rs in enumerate(settings):
         mean_gradients = torch.zeros_like(gaussian_means[i], requires_grad=True)
-        image, _radii = GaussianRasterizer(rs)(
+        out = GaussianRasterizer(rs)(
             means3D=gaussian_means[i], means2D=mean_gradients,
             shs=shs[i] if use_sh else None,
             colors_precomp=None if use_sh else shs[i, :, 0, :],
             opacities=gaussian_opacities[i, ..., None],
-            cov3D_precomp=gaussian_covariances[i, :, row, col])
-        images.append(image)
+            cov3D_precomp=gaussian_covariances[i, :, row, col], return_depth=return_depth)
+        images.append(out[0])
+        if return_depth:
+            depth = out[2]
+            if scale_invariant:
+                depth = depth / scale[i].to(depth.device)
+            depths.append(depth)
+            alphas.append(out[3])
+    if return_depth:
+        return torch.stack(images), torch.stack(depths), torch.stack(alphas)
     return torch.stack(images)
 
 

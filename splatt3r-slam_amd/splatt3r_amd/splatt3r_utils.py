@@ -427,8 +427,14 @@ class RenderCheck:
 
 
 @torch.inference_mode()
-def splatt3r_render(model, frame, ref_frame, K=None, target_T_WC=None, sizing=None):
+def splatt3r_render(model, frame, ref_frame, K=None, target_T_WC=None, sizing=None,
+                    return_depth=False):
     """splatt3r_utils.py:332-432 -> [1,1,3,H,W].
+
+    return_depth: (image [1,1,3,H,W], depth [1,1,H,W], alpha [1,1,H,W]) from
+    the same blend pass, depth = sum z_i alpha_i T_i in the frame's units and
+    alpha = sum alpha_i T_i, on both paths below (the RenderCheck rides on
+    the image and its re-render returns the same triple).
 
     sizing (RasterSizing, the frame loop): render without a host read of
     the instance count (rasterize_deferred); the image then carries a
@@ -459,21 +465,29 @@ def splatt3r_render(model, frame, ref_frame, K=None, target_T_WC=None, sizing=No
     import diff_gaussian_rasterization as dgr
     rs = settings[0]
 
+    s = float(scale[0])
+
+    def shaped(image, depth, alpha):
+        # the rasterizer ran on means * s: depth back in the frame's units
+        return image[None, None], (depth / s)[None, None], alpha[None, None]
+
     def two_call():
-        image, _ = dgr.GaussianRasterizer(rs)(means3D=means, means2D=torch.zeros_like(means),
-                                              shs=shs, colors_precomp=None, opacities=opac,
-                                              cov3D_precomp=cov6)
-        return image[None, None]
+        r = dgr.GaussianRasterizer(rs)(means3D=means, means2D=torch.zeros_like(means),
+                                       shs=shs, colors_precomp=None, opacities=opac,
+                                       cov3D_precomp=cov6, return_depth=return_depth)
+        return shaped(r[0], r[2], r[3]) if return_depth else r[0][None, None]
 
     if sizing is None or sizing.capacity is None:
         out = two_call()
         if sizing is not None:
             sizing.update(dgr.last_num_rendered)
         return out
-    image, _, info = dgr.rasterize_deferred(rs, means, opac, shs=shs, cov3D_precomp=cov6,
-                                            capacity=sizing.capacity, key_bits=sizing.key_bits)
-    out = image[None, None]
-    out._gsr_check = RenderCheck(info, two_call, sizing)
+    r = dgr.rasterize_deferred(rs, means, opac, shs=shs, cov3D_precomp=cov6,
+                               capacity=sizing.capacity, key_bits=sizing.key_bits,
+                               return_depth=return_depth)
+    info = r[2]
+    out = shaped(r[0], r[3], r[4]) if return_depth else r[0][None, None]
+    (out[0] if return_depth else out)._gsr_check = RenderCheck(info, two_call, sizing)
     return out
 
 
