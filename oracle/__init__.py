@@ -11,6 +11,20 @@ cpu_baseline leg may import this package; the product path
   tracker_ref.py  <- splatt3r_slam/tracker.py / geometry.py / nonlinear_optimizer.py
   net_ref.py      <- torch fp32 restatement of the MASt3RGaussians forward
   prng.py         <- portable splitmix64 weight generator (no reference counterpart)
+
+What pins the restatements to the reference: sim3_ref.c (exp, retr, act, the
+quat_comp / actSim3 parts of mul, inv through relSim3, pose_retr) and
+matching_ref.c (iter_proj, refine_matches) are checked bit for bit against the
+reference's own kernel text.  ref_build.py cuts the per-thread kernels out of
+the reference tree at build time (never into git), compiles them as host C++
+behind ref_shim/ into _ref/libref_kernels.so (`ref_lib()`, the `ref_*`
+wrappers below), and gen_golden.py records that library's outputs on the
+cases of ref_cases.py in tests/golden/ref_kernels.npz;
+tests/test_ref_kernels.py holds the restatements and the HIP kernels to that
+fixture.  Still restatement-only: prep_for_iter_proj / occlusion (Python in the
+reference, pinned by the img_gradient and host-glue fixtures), the lietorch
+quaternion re-normalisation in mul, Sim3 log, and the block-cooperative GN
+kernels (gn_backend_ref.py).
 """
 from __future__ import annotations
 
@@ -29,6 +43,8 @@ def build() -> str:
     r = subprocess.run(["make", "-s", "-C", HERE], capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"oracle build failed:\n{r.stdout}\n{r.stderr}")
+    from . import ref_build
+    ref_build.build()   # no reference tree: builds nothing, keeps oracle/_ref/ as it is
     return LIB
 
 
@@ -178,6 +194,126 @@ def match(X11, X21, D11, D21, idx_init=None, cfg=MATCH_CFG):
         p1 = refine_matches(D11h, D21h, p1, cfg["radius"], cfg["dilation_max"])
     idx = p1[..., 0] + w * p1[..., 1]
     return idx, valid[..., None]
+
+
+# ------------------------------------- the reference's own kernel text ----
+REF_LIB = os.path.join(HERE, "_ref", "libref_kernels.so")
+_ref = None
+
+
+def ref_lib():
+    """oracle/_ref/libref_kernels.so (the reference's per-thread kernels built
+    by ref_build.py), or None where it has not been built (no reference
+    tree).  Only fixture generation and the freshness test need it."""
+    global _ref
+    if _ref is None and os.path.exists(REF_LIB):
+        _ref = ctypes.CDLL(REF_LIB)
+    return _ref
+
+
+def _ref_fn(name):
+    L = ref_lib()
+    if L is None:
+        raise RuntimeError("oracle/_ref/libref_kernels.so is not built (oracle.build() with the "
+                           "reference tree present)")
+    return getattr(L, name)
+
+
+def ref_refine_matches(D11, D21, p1, radius, dilation_max):
+    """fp16 descriptors -> the c10::Half kernel, fp32 -> the float kernel."""
+    half = np.asarray(D11).dtype == np.float16
+    dt = np.float16 if half else np.float32
+    D11, D21 = _c(D11, dt), _c(D21, dt)
+    p1 = _c(p1, np.int64)
+    b, h, w, f = D11.shape
+    n = p1.shape[1]
+    out = np.zeros((b, n, 2), np.int64)
+    _ref_fn("ref_refine_matches_half" if half else "ref_refine_matches_float")(
+        _p(D11), _p(D21), _p(p1), _p(out), b, h, w, n, f, int(radius), int(dilation_max))
+    return out
+
+
+def ref_iter_proj(rays, pts, p_init, max_iter, lambda_init, cost_thresh):
+    rays, pts, p_init = _c(rays, np.float32), _c(pts, np.float32), _c(p_init, np.float32)
+    b, h, w, _ = rays.shape
+    n = p_init.shape[1]
+    p_new = np.zeros((b, n, 2), np.float32)
+    conv = np.zeros((b, n), np.uint8)
+    _ref_fn("ref_iter_proj")(_p(rays), _p(pts), _p(p_init), _p(p_new), _p(conv), b, h, w, n,
+                             int(max_iter), ctypes.c_float(lambda_init),
+                             ctypes.c_float(cost_thresh))
+    return p_new, conv.astype(bool)
+
+
+def ref_pose_retr(poses, dx, num_fix):
+    poses = _c(poses, np.float32).copy()
+    dx = _c(dx, np.float32)
+    _ref_fn("ref_pose_retr")(_p(poses), _p(dx), ctypes.c_int64(poses.shape[0]),
+                             ctypes.c_int64(num_fix))
+    return poses
+
+
+def _ref_rows(fn, dout, *ins):
+    """out[i] = fn(in0[i], in1[i], ...) over contiguous float32 rows."""
+    n = ins[0][0].shape[0]
+    out = np.empty((n, dout), np.float32)
+    _ref_fn(fn)(*[_p(a) for a, _ in ins], _p(out), ctypes.c_int64(n))
+    return out
+
+
+def _rows(a, d):
+    return (_c(a, np.float32).reshape(-1, d), d)
+
+
+def ref_sim3_exp(xi):
+    return _ref_rows("ref_sim3_exp_batch", 8, _rows(xi, 7))
+
+
+def ref_sim3_retr(T, xi):
+    return _ref_rows("ref_sim3_retr_batch", 8, _rows(T, 8), _rows(xi, 7))
+
+
+def ref_sim3_act(T, X):
+    T = _c(T, np.float32).reshape(-1, 8)
+    X = _c(X, np.float32).reshape(-1, 3)
+    Y = np.empty_like(X)
+    _ref_fn("ref_sim3_act_batch")(_p(T), ctypes.c_int64(T.shape[0]), _p(X), _p(Y),
+                                  ctypes.c_int64(X.shape[0]))
+    return Y
+
+
+def ref_sim3_mul(a, b):
+    """quat_comp / actSim3 composition, quaternion NOT re-normalised (see
+    lietorch_normalize)."""
+    return _ref_rows("ref_sim3_mul_batch", 8, _rows(a, 8), _rows(b, 8))
+
+
+def ref_sim3_rel(Ti, Tj):
+    """relSim3: Ti^-1 * Tj (with Tj the identity: the inverse)."""
+    return _ref_rows("ref_sim3_rel_batch", 8, _rows(Ti, 8), _rows(Tj, 8))
+
+
+def ref_sim3_adj_inv(T, X):
+    return _ref_rows("ref_sim3_adj_inv_batch", 7, _rows(T, 8), _rows(X, 7))
+
+
+def ref_huber(r):
+    return _ref_rows("ref_huber_batch", 1, _rows(r, 1))[:, 0]
+
+
+def lietorch_normalize(T):
+    """lietorch's Sim3 product re-normalises the quaternion (q / sqrt(q.q),
+    fp32, terms summed left to right, one reciprocal); the reference kernels
+    have no product of their own, so this step is stated here, once, for the
+    comparisons of `mul` against ref_sim3_mul."""
+    T = np.array(T, np.float32, copy=True)
+    q = T[:, 3:7]
+    n2 = q[:, 0] * q[:, 0]
+    for k in (1, 2, 3):
+        n2 = n2 + q[:, k] * q[:, k]
+    inv = np.float32(1.0) / np.sqrt(n2)
+    T[:, 3:7] = q * inv[:, None]
+    return T
 
 
 # ---------------------------------------------------------- rasterizer ----

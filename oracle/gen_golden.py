@@ -3,7 +3,7 @@ reference from /root/reference (this container only; the GPU box never reads
 /root/reference).  Committed outputs are data only (inputs + expected
 outputs), never reference source.
 
-  python oracle/gen_golden.py [section ...]     sections: matching, net, net_c4, n1, mono, resize, viz, portrait, render
+  python oracle/gen_golden.py [section ...]     sections: ref_kernels, matching, net, net_c4, n1, mono, resize, viz, portrait, render
 
 matching : splatt3r_slam/image.py img_gradient (imported) driven exactly as
            splatt3r_slam/matching.py:25-49 prep_for_iter_proj does.
@@ -22,7 +22,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-REF = "/root/reference"
+REF = os.environ.get("S3_REFERENCE_DIR", "/root/reference")
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(os.path.dirname(HERE), "tests", "golden")
 
@@ -1040,7 +1040,28 @@ def gen_host():
     print("wrote host_glue.npz")
 
 
-SECTIONS = {"host": gen_host, "matching": gen_matching, "render": gen_render, "net": gen_net, "net_c4": gen_net_c4, "net_c5": gen_net_c5, "n1": gen_n1, "mono": gen_mono, "resize": gen_resize, "viz": gen_viz, "portrait": gen_portrait}
+def gen_ref_kernels():
+    """Outputs of the reference's own per-thread kernels (refine_matches,
+    iter_proj, the Sim3 device functions, pose_retr), compiled for the host by
+    oracle/ref_build.py, on the cases of oracle/ref_cases.py
+    -> tests/golden/ref_kernels.npz (numeric arrays only)."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import oracle
+    from oracle import ref_cases
+    oracle.build()
+    if oracle.ref_lib() is None:
+        raise SystemExit("oracle/_ref/libref_kernels.so was not built")
+    fx = ref_cases.make_inputs()
+    fx.update(ref_cases.reference_outputs(fx))
+    path = os.path.join(GOLDEN, "ref_kernels.npz")
+    np.savez_compressed(path, **fx)
+    moved = {n: float(np.any(fx[f"rf_{n}_out"] != fx[f"rf_{n}_p1"], -1).mean())
+             for n in ref_cases.REFINE_CASES}
+    conv = {n: float(fx[f"ip_{n}_conv"][-1].mean()) for n in ref_cases.ITER_CASES}
+    print("wrote ref_kernels.npz", os.path.getsize(path), "bytes; moved", moved, "converged", conv)
+
+
+SECTIONS = {"ref_kernels": gen_ref_kernels, "host": gen_host, "matching": gen_matching, "render": gen_render, "net": gen_net, "net_c4": gen_net_c4, "net_c5": gen_net_c5, "n1": gen_n1, "mono": gen_mono, "resize": gen_resize, "viz": gen_viz, "portrait": gen_portrait}
 
 
 def main(argv):

@@ -15,8 +15,10 @@
  * semantics: product and running sum are each rounded to fp16 (RNE).
  * Initial best score = 0 (cuda::std::numeric_limits<c10::Half>::min() of the
  * unspecialised primary template).
- * Parity vs the CUDA reference binary: UNPINNED (no nvcc here, no reference
- * tests); pinned by the reference-importable img_gradient fixture and by
+ * iter_proj and refine_matches are pinned bit for bit to the reference's own
+ * kernel text, compiled for the host by oracle/ref_build.py
+ * (tests/golden/ref_kernels.npz, tests/test_ref_kernels.py); prep and the
+ * occlusion check by the reference-importable img_gradient fixture and by
  * planted-shift / self-match known answers in tests/.
  */
 #include <math.h>

@@ -11,13 +11,18 @@
  * Group product / inverse follow lietorch's Sim3 (t, q, s) composition rule
  * (external lietorch, unpinned; quaternion re-normalised after products as
  * lietorch's SO3 constructor does).  Parity vs lietorch itself: UNPINNED
- * (submodule absent); pinned instead by group identities in tests/.
+ * (submodule absent).  Everything restated from gn_kernels.cu is pinned bit
+ * for bit to that kernel text compiled for the host (oracle/ref_build.py,
+ * tests/golden/ref_kernels.npz, tests/test_ref_kernels.py), and by group
+ * identities in tests/.
  * Compile with -ffp-contract=off (strict evaluation of the source text).
  */
 #include <math.h>
 #include <stdint.h>
 
-#define EPS 1e-6f
+/* a double, as in gn_kernels.cu:33: `x < EPS` compares the float x in double, so
+ * x == 1e-6f (the last float below 1e-6) takes the small-angle branch */
+#define EPS 1e-6
 
 static void quat_comp(const float* qi, const float* qj, float* out) {
   float o0 = qi[3] * qj[0] + qi[0] * qj[3] + qi[1] * qj[2] - qi[2] * qj[1];

@@ -10,7 +10,13 @@
 
 namespace s3lie {
 
-constexpr float kEps = 1e-6f;  // gn_kernels.cu:33 (#define EPS 1e-6)
+constexpr float kEps = 1e-6f;  // lietorch's EPS (log_so3)
+
+// `x < EPS` of gn_kernels.cu:33 (#define EPS 1e-6): EPS is a double there, so
+// the float x is compared in double.  1e-6f (9.99999997e-7) is the last
+// float below the double 1e-6 and passes the test; `x < 1e-6f` would send it
+// to the other branch.  (tests/test_ref_kernels.py, regimes thr_*)
+S3_HD bool below_eps(float x) { return x <= 1e-6f; }
 
 // out = qi * qj  (gn_kernels.cu:177-184 quat_comp)
 S3_HD void quat_comp(const float* qi, const float* qj, float* out) {
@@ -83,7 +89,7 @@ S3_HD void inv_sim3(const float* a, float* out) {
 S3_HD void exp_so3(const float* phi, float* q) {
   float theta_sq = phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2];
   float imag, real;
-  if (theta_sq < kEps) {
+  if (below_eps(theta_sq)) {
     float theta_p4 = theta_sq * theta_sq;
     imag = (float)(0.5 - (1.0 / 48.0) * theta_sq + (1.0 / 3840.0) * theta_p4);
     real = (float)(1.0 - (1.0 / 8.0) * theta_sq + (1.0 / 384.0) * theta_p4);
@@ -100,9 +106,9 @@ S3_HD void sim3_w_coeffs(float theta_sq, float sigma, float scale, float* A,
                          float* B, float* C) {
   float theta = sqrtf(theta_sq);
   const float one = 1.0f, half = 0.5f;
-  if (fabsf(sigma) < kEps) {
+  if (below_eps(fabsf(sigma))) {
     *C = one;
-    if (fabsf(theta) < kEps) {
+    if (below_eps(fabsf(theta))) {
       *A = half;
       *B = (float)(1.0 / 6.0);
     } else {
@@ -111,7 +117,7 @@ S3_HD void sim3_w_coeffs(float theta_sq, float sigma, float scale, float* A,
     }
   } else {
     *C = (scale - one) / sigma;
-    if (fabsf(theta) < kEps) {
+    if (below_eps(fabsf(theta))) {
       float sigma_sq = sigma * sigma;
       *A = ((sigma - one) * scale + one) / sigma_sq;
       *B = (scale * half * sigma_sq + scale - one - sigma * scale) / (sigma_sq * sigma);

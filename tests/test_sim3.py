@@ -1,6 +1,9 @@
 """Sim3 group ops (lietorch replacement, include/s3lie.h) vs the oracle
-restatement of gn_kernels.cu:171-452.  Parity vs lietorch itself is unpinned
-(submodule absent); the oracle is pinned by group identities below."""
+restatement of gn_kernels.cu:171-452.  The restatement itself is pinned bit
+for bit to the reference's own kernel text by tests/test_ref_kernels.py
+(oracle/ref_build.py -> tests/golden/ref_kernels.npz) and by the group
+identities below; only lietorch's own parts (the quaternion re-normalisation
+of the product, log) stay unpinned (submodule absent)."""
 import ctypes
 
 import numpy as np
