@@ -75,8 +75,8 @@ typedef struct {
   /* split-K: split_k > 1 partitions the K tiles over split_k workgroups per
    * output tile; fp32 partials go to `workspace` (s3n_gemm_workspace_bytes)
    * and a second launch sums them in split order (deterministic) and
-   * applies the epilogue.  tile: 0 = auto, 1 = 64x64, 2 = 64x128,
-   * 3 = 128x128 (4 waves), 4 = 256x128 (8 waves), 5 = 128x128 (8 waves). */
+   * applies the epilogue.  tile: 0 = the library's static choice, or an id
+   * of the tile table (s3n_gemm_tile_info below; csrc/net_gemm_tiles.def). */
   int split_k;
   int tile;
   void* workspace;
@@ -103,7 +103,7 @@ typedef struct {
   int tail_n;
   int64_t ld_tail;
   /* Optional fragment-packed copy of each group's B for the B-direct tiles
-   * (70-77): Bp[nb][ks][lane][8] fp16 with nb = n / 16 (N padded to a
+   * (s3n_gemm_tile.bdirect): Bp[nb][ks][lane][8] fp16 with nb = n / 16 (N padded to a
    * multiple of 16 with zeros), ks = k / 32, lane = 16 * ((k % 32) / 8) +
    * n % 16, element k % 8; dense A only, K % 32 == 0.  NULL: those tiles
    * are unavailable (the other tiles never read it). */
@@ -112,6 +112,24 @@ typedef struct {
 
 size_t s3n_gemm_workspace_bytes(const s3n_gemm_args* args);
 int s3n_gemm(const s3n_gemm_args* args, void* stream);
+
+/* One entry of the tile table (csrc/net_gemm_tiles.def, the only place a
+ * tile is defined): the output tile bm x bn, the K tile bk, the in-workgroup
+ * K-groups kg and the MFMA shape mf (32 = 32x32x16, 16 = 16x16x32), which
+ * with the flags fix the summation order of a launch; regs_epilogue: the
+ * fp32 tile does not fit the LDS ring, so the per-register epilogue runs;
+ * halo: 3x3 conv tile with halo reuse (K order (ky, chunk, kx)); bdirect:
+ * reads the packed B (Bp); tail_ok: may carry the fused tail; tuner: offered
+ * to the tuner (0: launched only by an explicit tile id). */
+typedef struct {
+  int id, bm, bn, bk, kg, mf;
+  int regs_epilogue, halo, bdirect, tail_ok, tuner;
+} s3n_gemm_tile;
+
+/* Enumerate the tile table: index in [0, s3n_gemm_tile_count()); any other
+ * index is S3_ERR_INVALID.  Host only (no device is touched). */
+int s3n_gemm_tile_count(void);
+int s3n_gemm_tile_info(int index, s3n_gemm_tile* out);
 
 /* Tuning hook (not on the product path): flags applied to later s3n_gemm
  * launches; 1 = skip the MFMAs, 2 = skip the operand DMA, 4 = skip the

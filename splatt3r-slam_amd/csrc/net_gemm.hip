@@ -1,12 +1,38 @@
 // Grouped fp16 MFMA GEMM (include/s3n.h s3n_gemm): argument checks and the
-// C ABI.  The kernel template is net_gemm_kernel.hpp; its tile families are
-// instantiated in net_gemm_t1..t5.hip, the halo conv in net_gemm_t6.hip, the
-// B-direct tiles in net_gemm_t9.hip (compiled in parallel).
+// C ABI.  The kernel template is net_gemm_kernel.hpp; the tiles of
+// net_gemm_tiles.def are instantiated by the translation units
+// net_gemm_t1..t9.hip (compiled in parallel).
 #include "net_gemm_kernel.hpp"
 
 namespace s3gemm {
 int g_xcd_flags = 0;
 }  // namespace s3gemm
+
+#define S3_GEMM_UNIT_REF(n) {s3gemm::launch_t##n, s3gemm::sat_t##n},
+static const s3gemm::Unit kUnits[] = {S3_GEMM_UNITS(S3_GEMM_UNIT_REF)};
+#undef S3_GEMM_UNIT_REF
+
+// every line of the tile table, as s3n_gemm_tile_info reports it
+static const s3n_gemm_tile kTiles[] = {
+#define S3_TILE_GEMM(id, tail, tuner, BM, BN, S, NWM, NWN, BK, KG, MF) \
+  {id, BM, BN, BK, KG, MF, !vec_epilogue_fits(BM, BN, S, BK), 0, 0, tail, tuner},
+#define S3_TILE_PP(id, tail, tuner, BM, BN, S, NWM, NWN, MF) \
+  {id, BM, BN, 64, 1, MF, !vec_epilogue_fits(BM, BN, S, 64), 0, 0, tail, tuner},
+#define S3_TILE_HALO(id, tail, tuner, BM, BN, NWM, NWN, MF, PIPE, S) \
+  {id, BM, BN, 64, 1, MF, 0, 1, 0, tail, tuner},
+#define S3_TILE_BD(id, tail, tuner, BM, BN, NWM, NWN, S) \
+  {id, BM, BN, 64, 1, 16, 0, 0, 1, tail, tuner},
+#include "net_gemm_tiles.def"
+};
+constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
+
+extern "C" int s3n_gemm_tile_count(void) { return kNumTiles; }
+extern "C" int s3n_gemm_tile_info(int index, s3n_gemm_tile* out) {
+  S3_REQUIRE(out && index >= 0 && index < kNumTiles,
+             "s3n_gemm_tile_info: index %d outside 0..%d (or null out)", index, kNumTiles - 1);
+  *out = kTiles[index];
+  return S3_OK;
+}
 
 static int g_gemm_debug = 0;
 
@@ -14,9 +40,8 @@ int s3n_ln_f16_saturations(int reset);   // net_ops.hip
 
 extern "C" int s3n_f16_saturations(int reset) {
   int any = 0;
-  for (auto fn : {s3gemm::sat_t1, s3gemm::sat_t2, s3gemm::sat_t3, s3gemm::sat_t4, s3gemm::sat_t5,
-                  s3gemm::sat_t6, s3gemm::sat_t7, s3gemm::sat_t8, s3gemm::sat_t9}) {
-    const int v = fn(reset);
+  for (const s3gemm::Unit& u : kUnits) {
+    const int v = u.sat(reset);
     if (v < 0) return -1;
     any |= v;
   }
@@ -122,10 +147,8 @@ extern "C" int s3n_gemm(const s3n_gemm_args* a, void* stream) {
     S3_REQUIRE(p.ws, "s3n_gemm: split_k > 1 needs a workspace (s3n_gemm_workspace_bytes)");
   hipStream_t st = s3::as_stream(stream);
   // tile families live in their own translation units (net_gemm_t*.hip)
-  for (auto fn : {s3gemm::launch_t1, s3gemm::launch_t2, s3gemm::launch_t3, s3gemm::launch_t4,
-                  s3gemm::launch_t5, s3gemm::launch_t6, s3gemm::launch_t7,
-                  s3gemm::launch_t8, s3gemm::launch_t9}) {
-    const int r = fn(a->tile, p, st);
+  for (const s3gemm::Unit& u : kUnits) {
+    const int r = u.launch(a->tile, p, st);
     if (r != s3gemm::kNotMine) return r;
   }
   S3_REQUIRE(false, "s3n_gemm: unknown tile %d", a->tile);

@@ -1,14 +1,17 @@
 // Grouped fp16 MFMA GEMM with fused epilogues and an implicit-im2col
 // convolution A path (include/s3n.h s3n_gemm).
 //
-// Tile: BM x BN x 64 per 256-lane workgroup (4 waves as 2x2), each wave a
-// (BM/2)x(BN/2) block of v_mfma_f32_32x32x16_f16 accumulators.  Operands are
-// staged global -> registers -> LDS (double buffer, one barrier per K tile,
-// next tile's global loads issued before the current tile's MFMAs).  LDS
-// rows are 128 B (64 fp16); 16-B chunks are XOR-swizzled with (row>>1)&7 so
-// every ds_read_b128 lane group of the A/B fragment reads hits 16 distinct
-// 16-B slots of the 256-B bank row (conflict-free, guide §2/T2).  The tile
-// grid is remapped so that each XCD gets a contiguous run of tiles.
+// Tile: BM x BN x BK (BK = 64 or 128) per workgroup of NWM x NWN waves
+// (x KG K-groups, below), each wave a (BM/NWM) x (BN/NWN) block of
+// v_mfma_f32_32x32x16_f16 or v_mfma_f32_16x16x32_f16 accumulators (MF = 32 /
+// 16, AccT).  Operands go global -> LDS by LDS-DMA (raw buffer loads with the
+// LDS bit: out-of-range offsets read zero, which implements every M / N / K
+// tail and conv padding tap) into a ring of S stages: the tiles kt + 1 ..
+// kt + S - 2 stay in flight while tile kt is consumed, one raw barrier per K
+// step.  LDS rows are BK fp16; their 16-B chunks are XOR-swizzled (swz) so
+// every ds_read_b128 lane group of a fragment read hits 16 distinct 16-B
+// slots of a 256-B bank row.  The tile grid is remapped so that each XCD
+// gets a contiguous run (or a 2-D block, plan_grid) of tiles.
 //
 // In-workgroup split-K (KG > 1): a workgroup holds KG groups of NWM x NWN
 // waves on the same output tile; group kg consumes the K tiles
@@ -18,6 +21,14 @@
 // alone leaves one 4-wave workgroup per CU waiting on its DMA; KG groups give
 // each SIMD KG waves to overlap load latency with MFMA without the fp32
 // workspace round trip of a split-K launch.
+//
+// Epilogue: where the fp32 tile fits the ring (vec_epilogue_fits) and the
+// host found every operand aligned, the tile is staged in LDS and finished
+// in 8-column vector chunks (epilogue_vec); otherwise per accumulator
+// register (epilogue_regs, 32x32x16 only).
+//
+// The tiles (template arguments per tile id) are listed in
+// net_gemm_tiles.def and nowhere else.
 #include <algorithm>
 
 #pragma once
@@ -31,27 +42,28 @@ namespace s3gemm {
 typedef _Float16 f16;
 struct GemmP;
 extern int g_xcd_flags;   // tuning hook s3n_gemm_set_xcd_flags: 1 = band split only
-// launch the tile family of one translation unit; -1000 = tile not in it
-int launch_t1(int tile, const GemmP& p, hipStream_t st);
-int launch_t2(int tile, const GemmP& p, hipStream_t st);
-int launch_t3(int tile, const GemmP& p, hipStream_t st);
-int launch_t4(int tile, const GemmP& p, hipStream_t st);
-int launch_t5(int tile, const GemmP& p, hipStream_t st);
-int launch_t6(int tile, const GemmP& p, hipStream_t st);
-int launch_t7(int tile, const GemmP& p, hipStream_t st);
-int launch_t8(int tile, const GemmP& p, hipStream_t st);
-int launch_t9(int tile, const GemmP& p, hipStream_t st);
-// read (and optionally reset) one translation unit's fp16 saturation flag
-int sat_t1(int reset);
-int sat_t2(int reset);
-int sat_t3(int reset);
-int sat_t4(int reset);
-int sat_t5(int reset);
-int sat_t6(int reset);
-int sat_t7(int reset);
-int sat_t8(int reset);
-int sat_t9(int reset);
 constexpr int kNotMine = -1000;
+// One translation unit net_gemm_t<n>.hip: launch_t<n> launches one of its
+// tiles (kNotMine = the tile is not in it), sat_t<n> reads (and optionally
+// resets) its fp16 saturation flag.
+struct Unit {
+  int (*launch)(int tile, const GemmP& p, hipStream_t st);
+  int (*sat)(int reset);
+};
+#define S3_GEMM_UNITS(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9)
+#define S3_GEMM_UNIT_DECL(n)                                \
+  int launch_t##n(int tile, const GemmP& p, hipStream_t st); \
+  int sat_t##n(int reset);
+S3_GEMM_UNITS(S3_GEMM_UNIT_DECL)
+#undef S3_GEMM_UNIT_DECL
+
+// Whether the fp32 image of a BM x BN tile fits the S-stage operand ring:
+// then the LDS-staged vector epilogue (and the fused tail) can run.  The
+// kernels, their launch checks and the tile table (s3n_gemm_tile_info
+// regs_epilogue) all ask this one function.
+constexpr bool vec_epilogue_fits(int BM, int BN, int S, int BK) {
+  return BM * BN * 4 <= S * (BM + BN) * BK * 2;
+}
 }  // namespace s3gemm
 
 namespace s3gemm {
@@ -100,6 +112,7 @@ struct GemmP {
 namespace {
 using s3gemm::GemmP;
 using s3gemm::g_xcd_flags;
+using s3gemm::vec_epilogue_fits;
 typedef _Float16 f16;
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -879,7 +892,7 @@ k_gemm(GemmP p) {
   if (p.debug & 4) return;
   // the LDS-staged vector epilogue where the fp32 tile fits the ring (one
   // partial-tile slice per K-group, summed in group order inside)
-  constexpr bool kVecFits = BM * BN * 4 <= kStages * STAGE * 2;
+  constexpr bool kVecFits = vec_epilogue_fits(BM, BN, kStages, BK);
   if constexpr (kVecFits) {
     if (p.vec_epi) {
       // row pitch BN + 4 floats where it fits (rows 16 B apart in the banks)
@@ -1000,11 +1013,11 @@ __attribute__((unused)) static int launch_splitk_reduce(const GemmP& q, hipStrea
 template <int BM, int BN, int S, int NWM = 2, int NWN = 2, int BK = 64, int KG = 1, int MF = 32>
 int launch(const GemmP& p, hipStream_t st) {
   S3_REQUIRE(MF == 32 || p.vec_epi, "s3n_gemm: 16x16 MFMA tiles need the vector epilogue");
-  static_assert(MF == 32 || BM * BN * 4 <= S * (BM + BN) * BK * 2,
+  static_assert(MF == 32 || vec_epilogue_fits(BM, BN, S, BK),
                 "16x16 MFMA tiles stage their fp32 tile in the LDS ring");
   S3_REQUIRE(!p.tail_w[0] || p.N == BN,
              "s3n_gemm: the fused tail needs N == the tile width (%d, N = %d)", BN, p.N);
-  S3_REQUIRE(!p.tail_w[0] || BM * BN * 4 <= S * (BM + BN) * BK * 2,
+  S3_REQUIRE(!p.tail_w[0] || vec_epilogue_fits(BM, BN, S, BK),
              "s3n_gemm: the fused tail needs a tile whose fp32 image fits its LDS ring");
   S3_REQUIRE(KG == 1 || !p.tail_w[0], "s3n_gemm: the fused tail runs with one K-group");
   constexpr int NT = 64 * NWM * NWN * KG;

@@ -5,13 +5,13 @@
 namespace s3gemm {
 // 32x32x16 MFMA tiles with one K-group, and the default / fused-tail choice
 int launch_t1(int tile, const GemmP& p, hipStream_t st) {
-  if (tile == 1) return launch<64, 64, 3>(p, st);
-  if (tile == 2) return launch<64, 128, 3>(p, st);
-  if (tile == 3) return launch<128, 128, 2>(p, st);
-  if (tile == 6) return launch<64, 64, 4>(p, st);
-  if (tile == 7) return launch<64, 64, 5>(p, st);
-  if (tile == 8) return launch<64, 128, 4>(p, st);
-  if (tile != 0) return kNotMine;
+  switch (tile) {
+#define S3_TILE_UNIT 1
+#define S3_TILE_GEMM(id, tail, tuner, ...) case id: return launch<__VA_ARGS__>(p, st);
+#include "net_gemm_tiles.def"
+    case 0: break;   // the static choice below
+    default: return kNotMine;
+  }
   // the fused tail needs one column tile per row block
   if (p.tail_w[0]) {
     S3_REQUIRE(p.N == 64 || p.N == 128, "s3n_gemm: the fused tail needs N of 64 or 128");

@@ -5,12 +5,11 @@
 namespace s3gemm {
 // in-workgroup split-K: KG groups of 4 waves on one output tile
 int launch_t3(int tile, const GemmP& p, hipStream_t st) {
-  if (tile == 15) return launch<64, 64, 3, 2, 2, 64, 2>(p, st);
-  if (tile == 16) return launch<64, 64, 2, 2, 2, 64, 4>(p, st);
-  if (tile == 17) return launch<64, 128, 2, 2, 2, 64, 2>(p, st);
-  if (tile == 18) return launch<128, 128, 2, 2, 2, 64, 2>(p, st);
-  if (tile == 19) return launch<64, 64, 2, 2, 2, 128, 2>(p, st);
-  if (tile == 20) return launch<64, 128, 2, 2, 2, 64, 3>(p, st);
+  switch (tile) {
+#define S3_TILE_UNIT 3
+#define S3_TILE_GEMM(id, tail, tuner, ...) case id: return launch<__VA_ARGS__>(p, st);
+#include "net_gemm_tiles.def"
+  }
   return kNotMine;
 }
 int sat_t3(int reset) { return read_sat(reset); }

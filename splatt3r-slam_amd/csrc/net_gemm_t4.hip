@@ -3,20 +3,17 @@
 #include "net_gemm_kernel.hpp"
 
 namespace s3gemm {
-// v_mfma_f32_16x16x32 tiles: 4 waves (2 x 2), one large tile per CU (wave
-// tiles 32x80, 48x32, 64x48, 80x64, 128x64): the decomposition hipBLASLt
-// picks for the network's M = 768 shapes on gfx950.  A 16x16 tile needs the vector
-// epilogue (aligned operands).
+// v_mfma_f32_16x16x32 tiles, 4 waves.  They need the vector epilogue (aligned
+// operands); launch<> rejects a launch without it -- no silent fallback to
+// another tile, which would change the launch's reduction class
+// (ops.reduction_class); the tuner skips the error.
 int launch_t4(int tile, const GemmP& p, hipStream_t st) {
-  if (tile < 21 || tile > 25) return kNotMine;
-  // no silent fallback to another tile: that would change the launch's
-  // reduction class (ops.reduction_class); the tuner skips the error
-  S3_REQUIRE(p.vec_epi, "s3n_gemm: 16x16 MFMA tiles need the vector epilogue");
-  if (tile == 21) return launch<64, 160, 3, 2, 2, 64, 1, 16>(p, st);
-  if (tile == 22) return launch<96, 64, 3, 2, 2, 64, 1, 16>(p, st);
-  if (tile == 23) return launch<128, 96, 3, 2, 2, 64, 1, 16>(p, st);
-  if (tile == 24) return launch<160, 128, 3, 2, 2, 64, 1, 16>(p, st);
-  return launch<256, 128, 3, 2, 2, 64, 1, 16>(p, st);
+  switch (tile) {
+#define S3_TILE_UNIT 4
+#define S3_TILE_GEMM(id, tail, tuner, ...) case id: return launch<__VA_ARGS__>(p, st);
+#include "net_gemm_tiles.def"
+  }
+  return kNotMine;
 }
 int sat_t4(int reset) { return read_sat(reset); }
 }  // namespace s3gemm

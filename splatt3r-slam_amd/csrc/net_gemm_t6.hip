@@ -1,6 +1,6 @@
 // 3x3 / stride 1 / pad 1 implicit-GEMM convolution with halo reuse of the
-// input row segment (tiles 40-42; see net_gemm_kernel.hpp for the shared
-// epilogue and LDS-DMA helpers).
+// input row segment (the S3_TILE_HALO lines of net_gemm_tiles.def; see
+// net_gemm_kernel.hpp for the shared epilogue and LDS-DMA helpers).
 //
 // The generic conv path (k_gemm AMODE kConv) loads, for every K tile
 // (ky, kx, 64 input channels), the BM output pixels' tap pixels by LDS-DMA:
@@ -225,26 +225,12 @@ int launch_halo(const GemmP& p, hipStream_t st) {
 }  // namespace
 
 namespace s3gemm {
-// halo conv tiles: 128x128 (16x16x32 MFMA, 4 waves of 64x64), 256x64
-// (16x16x32, 4 waves of 128x32), 128x128 (32x32x16, 4 waves of 64x64);
-// 43, 45: 40 / 42 with the taps' fragment reads software-pipelined (the
-// 256x64 form would spill with them)
 int launch_t6(int tile, const GemmP& p, hipStream_t st) {
-  if (tile == 40) return launch_halo<128, 128, 2, 2, 16, false>(p, st);
-  if (tile == 41) return launch_halo<256, 64, 2, 2, 16, false>(p, st);
-  if (tile == 42) return launch_halo<128, 128, 2, 2, 32, false>(p, st);
-  if (tile == 43) return launch_halo<128, 128, 2, 2, 16, true>(p, st);
-  if (tile == 45) return launch_halo<128, 128, 2, 2, 32, true>(p, st);
-  // 8 waves (two per SIMD: one wave's LDS reads hide behind the other's MFMAs)
-  if (tile == 46) return launch_halo<128, 128, 2, 4, 16, false>(p, st);
-  if (tile == 47) return launch_halo<256, 64, 4, 2, 16, false>(p, st);
-  if (tile == 48) return launch_halo<128, 128, 2, 4, 32, false>(p, st);
-  if (tile == 49) return launch_halo<128, 128, 2, 4, 16, true>(p, st);
-  if (tile == 50) return launch_halo<256, 64, 4, 2, 16, true>(p, st);
-  // one super-stage, two workgroups per CU
-  if (tile == 51) return launch_halo<128, 128, 2, 2, 16, false, 1>(p, st);
-  if (tile == 52) return launch_halo<128, 128, 2, 2, 32, false, 1>(p, st);
-  if (tile == 53) return launch_halo<256, 64, 2, 2, 16, false, 1>(p, st);
+  switch (tile) {
+#define S3_TILE_UNIT 6
+#define S3_TILE_HALO(id, tail, tuner, ...) case id: return launch_halo<__VA_ARGS__>(p, st);
+#include "net_gemm_tiles.def"
+  }
   return kNotMine;
 }
 int sat_t6(int reset) { return read_sat(reset); }

@@ -9,18 +9,12 @@
 
 namespace s3gemm {
 int launch_t7(int tile, const GemmP& p, hipStream_t st) {
-  if (tile < 32 || tile > 37 || tile == 33) return kNotMine;
-  const bool mf16 = tile == 32 || tile == 36 || tile == 37;
-  // no silent fallback to another tile (it would change the reduction class)
-  S3_REQUIRE(!mf16 || p.vec_epi, "s3n_gemm: 16x16 MFMA tiles need the vector epilogue");
-  if (tile == 32) return launch<128, 128, 2, 2, 4, 64, 1, 16>(p, st);
-  if (tile == 34) return launch<256, 128, 2, 4, 2, 64, 1, 32>(p, st);
-  if (tile == 35) return launch<128, 256, 2, 2, 4, 64, 1, 32>(p, st);
-  if (tile == 36) return launch<256, 128, 3, 4, 2, 64, 1, 16>(p, st);
-  // (deep rings of 4-6 stages for the small 1536-row decoder grids were
-  // slower on every decoder shape: fewer workgroups per CU hide less of the
-  // per-step latency than the extra tiles in flight, profiles/r05c)
-  return launch<128, 128, 3, 2, 4, 64, 1, 16>(p, st);
+  switch (tile) {
+#define S3_TILE_UNIT 7
+#define S3_TILE_GEMM(id, tail, tuner, ...) case id: return launch<__VA_ARGS__>(p, st);
+#include "net_gemm_tiles.def"
+  }
+  return kNotMine;
 }
 int sat_t7(int reset) { return read_sat(reset); }
 }  // namespace s3gemm

@@ -219,7 +219,7 @@ k_gemm_pp(GemmP p) {
   }
 
   // ---- epilogue (same as k_gemm) ----
-  constexpr bool kVecFits = BM * BN * 4 <= S * STAGE * 2;
+  constexpr bool kVecFits = vec_epilogue_fits(BM, BN, S, BK);
   if constexpr (kVecFits) {
     if (p.vec_epi) {
       constexpr int LDT = BM * (BN + 4) * 4 <= S * STAGE * 2 ? BN + 4 : BN;
@@ -237,11 +237,11 @@ template <int BM, int BN, int S, int NWM, int NWN, int MF>
 int launch_pp(const GemmP& p, hipStream_t st) {
   constexpr int BK = 64;
   S3_REQUIRE(MF == 32 || p.vec_epi, "s3n_gemm: 16x16 MFMA tiles need the vector epilogue");
-  static_assert(MF == 32 || BM * BN * 4 <= S * (BM + BN) * BK * 2,
+  static_assert(MF == 32 || vec_epilogue_fits(BM, BN, S, BK),
                 "16x16 MFMA tiles stage their fp32 tile in the LDS ring");
   S3_REQUIRE(!p.tail_w[0] || p.N == BN,
              "s3n_gemm: the fused tail needs N == the tile width (%d, N = %d)", BN, p.N);
-  S3_REQUIRE(!p.tail_w[0] || BM * BN * 4 <= S * (BM + BN) * BK * 2,
+  S3_REQUIRE(!p.tail_w[0] || vec_epilogue_fits(BM, BN, S, BK),
              "s3n_gemm: the fused tail needs a tile whose fp32 image fits its LDS ring");
   constexpr int NT = 64 * NWM * NWN;
   const GemmP q = plan_grid(p, BM, BN, BK);
@@ -260,21 +260,12 @@ int launch_pp(const GemmP& p, hipStream_t st) {
 
 namespace s3gemm {
 int launch_t8(int tile, const GemmP& p, hipStream_t st) {
-  if (tile < 60 || tile > 68) return kNotMine;
-  if (tile == 61) return kNotMine;   // 256 x 128 with 32x32 MFMAs spills (576 B/lane)
-  // the 16x16 tiles stage their fp32 tile through LDS: no silent fallback to
-  // another tile (that would change the launch's reduction class)
-  S3_REQUIRE(tile == 65 || p.vec_epi, "s3n_gemm: 16x16 MFMA tiles need the vector epilogue");
   switch (tile) {
-    case 60: return launch_pp<256, 128, 3, 2, 2, 16>(p, st);   // wave 128 x 64
-    case 62: return launch_pp<128, 256, 3, 2, 2, 16>(p, st);   // wave 64 x 128
-    case 63: return launch_pp<128, 128, 2, 2, 2, 16>(p, st);   // 64 KiB: 2 workgroups per CU
-    case 64: return launch_pp<192, 128, 3, 2, 2, 16>(p, st);   // wave 96 x 64
-    case 65: return launch_pp<128, 128, 2, 2, 2, 32>(p, st);
-    case 66: return launch_pp<128, 192, 3, 2, 2, 16>(p, st);   // wave 64 x 96
-    case 67: return kNotMine;   // 256 x 256: the fp32 tile does not fit the 2-stage ring
-    default: return launch_pp<256, 128, 3, 4, 2, 16>(p, st);   // 8 waves, wave 64 x 64
+#define S3_TILE_UNIT 8
+#define S3_TILE_PP(id, tail, tuner, ...) case id: return launch_pp<__VA_ARGS__>(p, st);
+#include "net_gemm_tiles.def"
   }
+  return kNotMine;
 }
 int sat_t8(int reset) { return read_sat(reset); }
 }  // namespace s3gemm

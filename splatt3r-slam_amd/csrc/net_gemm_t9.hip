@@ -220,25 +220,13 @@ int launch_bd(const GemmP& p, hipStream_t st) {
 }  // namespace
 
 namespace s3gemm {
-// tiles 70-79 (ops._BDIRECT); launch configurations measured against the
-// LDS-staged tiles of the same reduction class on the network's dense shapes
-// (tools/bench_gemm_bd.py, profiles/r06b_gemm_bdirect.log)
 int launch_t9(int tile, const GemmP& p, hipStream_t st) {
   switch (tile) {
-    case 70: return launch_bd<64, 128, 1, 4, 3>(p, st);    // wave 64 x 32
-    case 71: return launch_bd<64, 128, 1, 4, 2>(p, st);    // double-buffered
-    case 72: return launch_bd<64, 64, 1, 4, 3>(p, st);     // wave 64 x 16
-    case 73: return launch_bd<64, 64, 1, 4, 4>(p, st);
-    case 74: return launch_bd<128, 128, 1, 4, 4>(p, st);   // wave 128 x 32
-    case 75: return launch_bd<128, 128, 1, 4, 3>(p, st);
-    case 76: return launch_bd<128, 128, 2, 4, 3>(p, st);   // 8 waves, wave 64 x 32
-    case 77: return launch_bd<64, 128, 1, 4, 4>(p, st);
-    // 6-stage rings (5 K tiles in flight) for the latency-bound decoder
-    // launches: B needs no LDS, so a stage is only the A tile (8 KiB at BM 64)
-    case 78: return launch_bd<64, 64, 1, 4, 6>(p, st);
-    case 79: return launch_bd<64, 128, 1, 4, 6>(p, st);
-    default: return kNotMine;
+#define S3_TILE_UNIT 9
+#define S3_TILE_BD(id, tail, tuner, ...) case id: return launch_bd<__VA_ARGS__>(p, st);
+#include "net_gemm_tiles.def"
   }
+  return kNotMine;
 }
 int sat_t9(int reset) { return read_sat(reset); }
 }  // namespace s3gemm

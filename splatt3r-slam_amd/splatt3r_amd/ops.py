@@ -9,7 +9,9 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import functools
 import os
+import types
 from typing import Sequence
 
 import torch
@@ -58,12 +60,20 @@ class AttnArgs(ctypes.Structure):
     ]
 
 
+class GemmTile(ctypes.Structure):
+    """s3n_gemm_tile (include/s3n.h): one line of csrc/net_gemm_tiles.def."""
+    _fields_ = [(f, ctypes.c_int) for f in ("id", "bm", "bn", "bk", "kg", "mf", "regs_epilogue",
+                                            "halo", "bdirect", "tail_ok", "tuner")]
+
+
 _GP = ctypes.POINTER(GemmArgs)
 _AP = ctypes.POINTER(AttnArgs)
 _PP = ctypes.POINTER(P)
 _lib.register({
     "s3n_gemm": (ctypes.c_int, [_GP, P]),
     "s3n_gemm_workspace_bytes": (ctypes.c_size_t, [_GP]),
+    "s3n_gemm_tile_count": (ctypes.c_int, []),
+    "s3n_gemm_tile_info": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(GemmTile)]),
     "s3n_gemm_set_debug": (None, [ctypes.c_int]),
     "s3n_gemm_set_xcd_flags": (None, [ctypes.c_int]),
     "s3n_attention_set_variant": (None, [ctypes.c_int]),
@@ -97,8 +107,9 @@ ACT = {"none": 0, "gelu": 1, "relu": 2}
 # S3_SYNC_DEBUG=1: run plans op by op with a device sync after each (fault
 # localisation); S3_GRAPHS=0 disables HIP-graph capture.
 DEBUG_SYNC = os.environ.get("S3_SYNC_DEBUG", "0") == "1"
-# tuning overrides for experiments: S3_GEMM_TILE=<1..8> replaces the
-# library's automatic tile choice (only where a call leaves tile=0)
+# tuning overrides for experiments: S3_GEMM_TILE=<id of the tile table,
+# csrc/net_gemm_tiles.def> replaces the library's automatic tile choice (only
+# where a call leaves tile=0)
 TILE_OVERRIDE = int(os.environ.get("S3_GEMM_TILE", "0"))
 GRAPHS_ENABLED = os.environ.get("S3_GRAPHS", "1") != "0"
 # S3_ATTN_VARIANT=<n>: the no-RoPE attention kernel variant (net_attn.hip
@@ -196,7 +207,7 @@ _DB_STATE = {"loaded": set(), "entries": {}}
 
 def _kernel_abi() -> str:
     """Digest of the GEMM kernel sources (csrc/net_gemm*.hip, the kernel
-    template header and common.hpp): any edit of a kernel or of a launch
+    template header, the tile table and common.hpp): any edit of a kernel or of a launch
     precondition changes it, and a database written under another digest
     (its "abi" field) is ignored -- no stale tile choice is replayed after a
     kernel change.  "unknown" when the sources are not beside the package."""
@@ -205,6 +216,7 @@ def _kernel_abi() -> str:
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
     files = sorted(glob.glob(os.path.join(csrc, "net_gemm*.hip")) +
                    glob.glob(os.path.join(csrc, "net_gemm*.hpp")) +
+                   glob.glob(os.path.join(csrc, "net_gemm*.def")) +
                    [os.path.join(csrc, "common.hpp")])
     if not all(os.path.isfile(f) for f in files) or len(files) < 3:
         return "unknown"
@@ -226,62 +238,42 @@ def _flush_buffer(dev):
     return _FLUSH[dev]
 
 
-_TILE_SHAPES = {1: (64, 64), 2: (64, 128), 3: (128, 128), 4: (256, 128), 5: (128, 128),
-                6: (64, 64), 8: (64, 128), 9: (64, 64), 10: (64, 64), 11: (64, 128),
-                12: (128, 128), 14: (256, 256),
-                # in-workgroup K-groups (net_gemm.hip KG > 1)
-                15: (64, 64), 16: (64, 64), 17: (64, 128), 18: (128, 128), 19: (64, 64),
-                20: (64, 128),
-                # v_mfma_f32_16x16x32 tiles, 4 waves (net_gemm_t4/t5.hip)
-                21: (64, 160), 22: (96, 64), 23: (128, 96), 24: (160, 128), 25: (256, 128),
-                26: (64, 64), 27: (128, 128), 28: (64, 128), 29: (96, 128), 30: (64, 192),
-                31: (64, 64),
-                # 8 / 16 waves per workgroup (net_gemm_t7.hip)
-                32: (128, 128), 34: (256, 128), 35: (128, 256), 36: (256, 128), 37: (128, 128),
-                # 3x3 conv with halo reuse of the input row segment (net_gemm_t6.hip)
-                40: (128, 128), 41: (256, 64), 42: (128, 128), 43: (128, 128), 45: (128, 128),
-                46: (128, 128), 47: (256, 64), 48: (128, 128), 49: (128, 128), 50: (256, 64),
-                51: (128, 128), 52: (128, 128), 53: (256, 64),
-                # k_gemm_pp: fragment reads of half a K tile overlap the MFMAs
-                # of the other half (net_gemm_t8.hip)
-                63: (128, 128), 65: (128, 128), 68: (256, 128),
-                # B fragments straight from the packed weights into registers,
-                # A through the LDS ring (net_gemm_t9.hip)
-                70: (64, 128), 71: (64, 128), 72: (64, 64), 73: (64, 64), 74: (128, 128),
-                75: (128, 128), 76: (128, 128), 77: (64, 128), 78: (64, 64), 79: (64, 128)}
-# the B-direct tiles: dense A, a packed B (packed_b), no fused tail
-_BDIRECT = set(range(70, 80))
-_TAIL_OK = {1, 2, 3, 4, 5, 6, 8, 9, 10, 11, 12, 14, 40, 42, 43, 45, 46, 48, 49, 51, 52, 63, 65}
-# S3_GEMM_MF16=0: leave the 16x16x32 tile family out of the tuner (A/B)
-_EXCLUDED = set(range(21, 32)) if os.environ.get("S3_GEMM_MF16", "1") == "0" else set()
+@functools.lru_cache(maxsize=None)
+def tile_table():
+    """The library's tile table (csrc/net_gemm_tiles.def through
+    s3n_gemm_tile_info), read on first use.  `all`: every built tile by id.
+    The other views hold only the tiles offered to the tuner, in id order:
+    shapes id -> (BM, BN); red id -> (K tile, in-workgroup K-groups, MFMA
+    shape: 32 = 32x32x16, 16 = 16x16x32), the reduction structure;
+    regs_epilogue: the fp32 tile does not fit the LDS ring (per-register
+    epilogue); halo: K tiles in (ky, channel chunk, kx) order instead of
+    (ky, kx, channel chunk); tail_ok: may carry the fused tail; bdirect:
+    dense A, a packed B (packed_b), no fused tail."""
+    L = _lib.lib()
+    rows = [GemmTile() for _ in range(L.s3n_gemm_tile_count())]
+    for i, t in enumerate(rows):
+        _lib.check(L.s3n_gemm_tile_info(i, ctypes.byref(t)), "s3n_gemm_tile_info")
+    offered = sorted((t for t in rows if t.tuner), key=lambda t: t.id)
+    flags = {f: {t.id for t in offered if getattr(t, f)}
+             for f in ("regs_epilogue", "halo", "tail_ok", "bdirect")}
+    return types.SimpleNamespace(all={t.id: t for t in rows},
+                                 shapes={t.id: (t.bm, t.bn) for t in offered},
+                                 red={t.id: (t.bk, t.kg, t.mf) for t in offered}, **flags)
 
 
+@functools.lru_cache(maxsize=None)
+def _excluded() -> frozenset:
+    """Tiles the A/B switches leave out of the tuner: S3_GEMM_MF16=0 the
+    4-wave 16x16x32 family (tiles 21-31), S3_GEMM_HALO=0 the halo-reuse conv
+    tiles, S3_GEMM_BDIRECT=0 the B-direct tiles."""
+    out = set(range(21, 32)) if os.environ.get("S3_GEMM_MF16", "1") == "0" else set()
+    if os.environ.get("S3_GEMM_HALO", "1") == "0":
+        out |= tile_table().halo
+    if os.environ.get("S3_GEMM_BDIRECT", "1") == "0":
+        out |= tile_table().bdirect
+    return frozenset(out)
 
-# Reduction structure of each tile (net_gemm_t*.hip launch<BM, BN, S, NWM,
-# NWN, BK, KG, MF> arguments): K tile, in-workgroup K-groups, MFMA shape
-# (32 = 32x32x16, 16 = 16x16x32), and whether the fp32 tile fits the LDS
-# ring (vector epilogue) or takes the per-register epilogue.
-_TILE_RED = {1: (64, 1, 32), 2: (64, 1, 32), 3: (64, 1, 32), 4: (64, 1, 32), 5: (64, 1, 32),
-             6: (64, 1, 32), 8: (64, 1, 32), 9: (128, 1, 32), 10: (128, 1, 32),
-             11: (128, 1, 32), 12: (128, 1, 32), 14: (64, 1, 32),
-             15: (64, 2, 32), 16: (64, 4, 32), 17: (64, 2, 32), 18: (64, 2, 32),
-             19: (128, 2, 32), 20: (64, 3, 32),
-             **{t: (64, 1, 16) for t in range(21, 31)}, 31: (128, 1, 16),
-             32: (64, 1, 16), 34: (64, 1, 32), 35: (64, 1, 32), 36: (64, 1, 16), 37: (64, 1, 16),
-             40: (64, 1, 16), 41: (64, 1, 16), 42: (64, 1, 32), 43: (64, 1, 16),
-             45: (64, 1, 32), 46: (64, 1, 16), 47: (64, 1, 16), 48: (64, 1, 32), 49: (64, 1, 16),
-             50: (64, 1, 16), 51: (64, 1, 16), 52: (64, 1, 32), 53: (64, 1, 16),
-             63: (64, 1, 16), 65: (64, 1, 32), 68: (64, 1, 16),
-             **{t: (64, 1, 16) for t in range(70, 80)}}
-_REGS_EPILOGUE = {14, 34, 35}   # the fp32 tile does not fit the LDS ring
-# K tiles in (ky, channel chunk, kx) order instead of (ky, kx, channel chunk)
-_HALO = set(range(40, 54)) - {44}
-# S3_GEMM_HALO=0: leave the halo-reuse conv tiles out of the tuner (A/B)
-if os.environ.get("S3_GEMM_HALO", "1") == "0":
-    _EXCLUDED |= _HALO
-# S3_GEMM_BDIRECT=0: leave the B-direct tiles out of the tuner (A/B)
-if os.environ.get("S3_GEMM_BDIRECT", "1") == "0":
-    _EXCLUDED |= _BDIRECT
+
 # S3_GEMM_BDIRECT_OFF=enc,pair: no packed B (so no B-direct tile) for the
 # GEMMs of the plans built in those scopes (plan_scope; diagnostic A/B)
 _BD_OFF = set(filter(None, os.environ.get("S3_GEMM_BDIRECT_OFF", "").split(",")))
@@ -300,8 +292,9 @@ def plan_scope(name):
 
 def _db_digest() -> str:
     import hashlib
-    tables = (sorted(_TILE_SHAPES.items()), sorted(_TILE_RED.items()), sorted(_REGS_EPILOGUE),
-              sorted(_HALO), sorted(_TAIL_OK), sorted(_BDIRECT))
+    t = tile_table()
+    tables = (sorted(t.shapes.items()), sorted(t.red.items()), sorted(t.regs_epilogue),
+              sorted(t.halo), sorted(t.tail_ok), sorted(t.bdirect))
     return hashlib.sha1(repr(tables).encode()).hexdigest()[:16]
 
 
@@ -347,7 +340,7 @@ def _db_load(dev=None):
         return
     for k, v in db["entries"]:
         key, val = (db_arch,) + _db_decode(k), (int(v[0]), int(v[1]))
-        if val[0] in _EXCLUDED or (val[0] and val[0] not in _TILE_SHAPES):
+        if val[0] in _excluded() or (val[0] and val[0] not in tile_table().shapes):
             continue
         _DB_STATE["entries"][key] = val
         _TUNE_CACHE.setdefault(key, val)
@@ -385,11 +378,12 @@ def reduction_class(K: int, tile: int, split_k: int):
     order) and the epilogue form.  Two launches of one class compute
     bit-identical elements whatever their M or tile footprint (BM, BN only
     decide which workgroup computes an element)."""
-    bk, kg, mf = _TILE_RED[tile]
+    t = tile_table().all[tile]   # any built tile, offered to the tuner or not
+    bk, kg, mf = t.bk, t.kg, t.mf
     kt = -(-K // bk)
     per = -(-kt // max(1, split_k))
     bound = per * bk if -(-kt // per) > 1 else 0
-    return (mf, kg, bk if kg > 1 else 0, bound, tile in _REGS_EPILOGUE, tile in _HALO)
+    return (mf, kg, bk if kg > 1 else 0, bound, bool(t.regs_epilogue), bool(t.halo))
 
 
 def _tune_key(a):
@@ -402,20 +396,21 @@ def _tune_key(a):
 
 def _tune_candidates(a, split_ok, like=None):
     kt = -(-a.K // 64)
+    t = tile_table()
     out = []
-    for tile, (bm, bn) in _TILE_SHAPES.items():
-        if tile in _EXCLUDED:
+    for tile, (bm, bn) in t.shapes.items():
+        if tile in _excluded():
             continue
-        if a.tail_n and (bn != a.N or tile not in _TAIL_OK):
+        if a.tail_n and (bn != a.N or tile not in t.tail_ok):
             continue
-        if tile in _HALO and not (a.a_mode == 1 and a.ksize == 3 and a.stride == 1 and
+        if tile in t.halo and not (a.a_mode == 1 and a.ksize == 3 and a.stride == 1 and
                                   a.oW % bm == 0 and a.cC % 64 == 0):
             continue
-        if tile in _BDIRECT and not (a.Bp[0] and a.a_mode == 0 and not a.tail_n and a.K % 32 == 0):
+        if tile in t.bdirect and not (a.Bp[0] and a.a_mode == 0 and not a.tail_n and a.K % 32 == 0):
             continue
         tiles = a.groups * -(-a.M // bm) * -(-a.N // bn)
         for sk in (1, 2, 3, 4, 6, 8):
-            if sk > 1 and tile in _HALO:
+            if sk > 1 and tile in t.halo:
                 continue
             if like is not None:
                 # batch-invariant plan: only launches whose elements equal

@@ -43,7 +43,7 @@ def test_excluded_and_unknown_tiles_are_retuned(tmp_path, monkeypatch, fresh_db_
     p = tmp_path / "db.json"
     ents = [[[1, 1, 1, None], [51, 1]], [[2, 2, 2, None], [999, 1]], [[3, 3, 3, None], [32, 2]]]
     p.write_text(json.dumps({"digest": ops._db_digest(), "abi": ops._KERNEL_ABI, "entries": ents}))
-    monkeypatch.setattr(ops, "_EXCLUDED", set(ops._HALO))
+    monkeypatch.setattr(ops, "_excluded", lambda: set(ops.tile_table().halo))
     assert _reload(monkeypatch, p) == {("gfx950", 3, 3, 3, None): (32, 2)}
 
 
@@ -62,7 +62,7 @@ def test_shipped_database_matches_this_tree():
         db = json.load(f)
     assert db["digest"] == ops._db_digest()
     for k, v in db["entries"]:
-        assert v[0] == 0 or v[0] in ops._TILE_SHAPES
+        assert v[0] == 0 or v[0] in ops.tile_table().shapes
         if k[-1] is not None and v[0] and k[-1][0]:
             # a batch-invariant plan's choice is in the class of its like
             kk = k[2]

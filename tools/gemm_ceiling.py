@@ -48,7 +48,7 @@ def main():
     ap.add_argument("--tiles", default="")
     ap.add_argument("--splits", default="1")
     a = ap.parse_args()
-    tiles = [int(t) for t in a.tiles.split(",") if t] or sorted(ops._TILE_SHAPES)
+    tiles = [int(t) for t in a.tiles.split(",") if t] or sorted(ops.tile_table().shapes)
     splits = [int(s) for s in a.splits.split(",")]
     for sh in a.shapes.split(","):
         M, N, K, g = (int(x) for x in sh.split("x"))
@@ -61,7 +61,7 @@ def main():
         ref = [(A[i].float() @ B[i].float().T) for i in range(g)]
         res = []
         for t in tiles:
-            if t in ops._HALO:
+            if t in ops.tile_table().halo:
                 continue
             for sk in splits:
                 try:
