@@ -70,6 +70,7 @@ SOURCES = {
     "gn_backend.hip": STRICT,
     "retrieval.hip": STRICT,
     "ingest.hip": STRICT,
+    "photometric.hip": STRICT,
 }
 
 

@@ -58,6 +58,12 @@ SIGNATURES: dict[str, tuple] = {
     "s3m_prep_iter_proj": (I32, [P, P, P, P, P, P, I32, I32, I32, P]),
     "s3m_occlusion": (I32, [P, P, P, P, P, P, I32, I32, I32, F32, P]),
     "s3m_pixel_to_lin": (I32, [P, P, I64, I32, P]),
+    # s3p.h
+    "s3p_workspace_bytes": (SZ, [I32, I32, I32, I32]),
+    "s3p_derivs_bytes": (SZ, [I32, I32, I32, I32]),
+    "s3p_forward": (I32, [P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P]),
+    "s3p_backward": (I32, [P, P, P, P, P, P, I32, I32, I32, I32, P, P]),
+    "s3p_window": (None, [P]),
 }
 
 _lock = threading.Lock()

@@ -17,6 +17,11 @@ Same function names, argument meaning and file bytes as the reference:
 * `save_keyframes` (evaluate.py:74-85): `{t}.png` per keyframe (PIL instead
   of cv2; cv2's BGR swap followed by its BGR->RGB write is the identity).
 
+Render quality has no counterpart in the reference's evaluate.py (its numbers
+come from splatt3r_core/main.py log_metrics): `eval_renders`,
+`eval_keyframe_renders` and `save_render_metrics` score rendered against
+camera images on the device (splatt3r_amd/photometric.py).
+
 save_reconstruction's use_calib branch constrains points to their pixel
 rays first (evaluate.py:55-59).  save_traj's `intrinsics` branch calls
 `intrinsics.refine_pose_with_calibration(keyframe)` (evaluate.py:42), a
@@ -129,3 +134,80 @@ def save_keyframes(savedir, timestamps, keyframes):
         kf = keyframes[i]
         t = timestamps[kf.frame_id]
         Image.fromarray((kf.uimg.cpu().numpy() * 255).astype(np.uint8)).save(savedir / f"{t}.png")
+
+
+# ------------------------------------------------------- render quality ----
+METRIC_NAMES = ("mse", "psnr", "ssim")
+
+
+def eval_renders(renders, targets, masks=None):
+    """Score rendered images against camera images on the device
+    (photometric.image_metrics: the reference's log_metrics numbers,
+    main.py:249-258).  renders, targets: [N, C, H, W] float32 in [0, 1];
+    masks: [N, H, W] or None.  Returns (rows, means): one dict of mse, psnr,
+    ssim, l1 per image and the dict of their means over the images."""
+    from splatt3r_amd.photometric import image_metrics
+    m = {k: v.cpu().tolist() for k, v in image_metrics(renders, targets, masks).items()}
+    rows = [{k: m[k][i] for k in m} for i in range(renders.shape[0])]
+    means = {k: float(np.mean(v)) if v else float("nan") for k, v in m.items()}
+    return rows, means
+
+
+def save_render_metrics(logdir, logfile, timestamps, rows):
+    """One line `t mse psnr ssim` per image and a final `# mean mse psnr ssim`
+    line (the means over the lines above)."""
+    logdir = pathlib.Path(logdir)
+    logdir.mkdir(exist_ok=True, parents=True)
+    with open(logdir / logfile, "w") as f:
+        for t, r in zip(timestamps, rows):
+            f.write(" ".join([str(t)] + [repr(float(r[k])) for k in METRIC_NAMES]) + "\n")
+        means = [float(np.mean([r[k] for r in rows])) if rows else float("nan")
+                 for k in METRIC_NAMES]
+        f.write(" ".join(["# mean"] + [repr(v) for v in means]) + "\n")
+
+
+def load_render_metrics(path):
+    """Reader for the files save_render_metrics writes: (timestamps as
+    written, rows, means)."""
+    ts, rows, means = [], [], None
+    with open(path) as f:
+        for line in f:
+            p = line.split()
+            if p[:2] == ["#", "mean"]:
+                means = dict(zip(METRIC_NAMES, map(float, p[2:])))
+            else:
+                ts.append(p[0])
+                rows.append(dict(zip(METRIC_NAMES, map(float, p[1:]))))
+    return ts, rows, means
+
+
+def keyframe_target(kf):
+    """A keyframe's camera image as [1, 3, H, W] in [0, 1]: `uimg` ([H, W, 3])
+    or, for frames made from an already normalised tensor (which carry no
+    uimg), ImgNorm undone on `img`."""
+    if kf.uimg is not None:
+        return kf.uimg.to(kf.img.device, torch.float32).permute(2, 0, 1)[None]
+    return kf.img.to(torch.float32) * 0.5 + 0.5
+
+
+def eval_keyframe_renders(model, keyframes, K=None):
+    """Render every keyframe at its own pose (splatt3r_render(model, kf, kf,
+    K=K)) and score it against the keyframe's camera image.  Keyframes without
+    Gaussian predictions are skipped and counted.  Returns a dict: `rows`
+    (each with the keyframe's `frame_id`), `means`, `skipped`."""
+    from splatt3r_amd.splatt3r_utils import splatt3r_render
+    ids, renders, targets, skipped = [], [], [], 0
+    for i in range(len(keyframes)):
+        kf = keyframes[i]
+        if kf.gaussian_pred is None or kf.gaussian_pred_cross is None:
+            skipped += 1
+            continue
+        renders.append(splatt3r_render(model, kf, kf, K=K)[0])
+        targets.append(keyframe_target(kf))
+        ids.append(kf.frame_id)
+    rows, means = [], {}
+    if renders:
+        rows, means = eval_renders(torch.cat(renders).contiguous(), torch.cat(targets).contiguous())
+        for fid, r in zip(ids, rows):
+            r["frame_id"] = fid
+    return dict(rows=rows, means=means, skipped=skipped)
