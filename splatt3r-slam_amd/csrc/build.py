@@ -71,6 +71,7 @@ SOURCES = {
     "retrieval.hip": STRICT,
     "ingest.hip": STRICT,
     "photometric.hip": STRICT,
+    "loss_mask.hip": STRICT,
 }
 
 

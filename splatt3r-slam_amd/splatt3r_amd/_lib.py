@@ -64,6 +64,9 @@ SIGNATURES: dict[str, tuple] = {
     "s3p_forward": (I32, [P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P]),
     "s3p_backward": (I32, [P, P, P, P, P, P, I32, I32, I32, I32, P, P]),
     "s3p_window": (None, [P]),
+    # s3c.h
+    "s3c_loss_mask_workspace_bytes": (SZ, [I32, I32, I32]),
+    "s3c_loss_mask": (I32, [P, P, P, P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P]),
 }
 
 _lock = threading.Lock()

@@ -20,7 +20,9 @@ Same function names, argument meaning and file bytes as the reference:
 Render quality has no counterpart in the reference's evaluate.py (its numbers
 come from splatt3r_core/main.py log_metrics): `eval_renders`,
 `eval_keyframe_renders` and `save_render_metrics` score rendered against
-camera images on the device (splatt3r_amd/photometric.py).
+camera images on the device (splatt3r_amd/photometric.py), and
+`eval_novel_view_renders` scores a keyframe against its neighbour's Gaussians
+over the co-visibility mask (splatt3r_amd/loss_mask.py).
 
 save_reconstruction's use_calib branch constrains points to their pixel
 rays first (evaluate.py:55-59).  save_traj's `intrinsics` branch calls
@@ -211,3 +213,57 @@ def eval_keyframe_renders(model, keyframes, K=None):
         for fid, r in zip(ids, rows):
             r["frame_id"] = fid
     return dict(rows=rows, means=means, skipped=skipped)
+
+
+def _own_depth(model, kf, K, alpha_min):
+    """A keyframe's rendered depth at its own pose, [1, 1, H, W]: depth / alpha
+    (the blend pass returns sum z_i alpha_i T_i) where alpha >= alpha_min,
+    else 0, which the loss mask's depth > 1e-6 condition drops."""
+    from splatt3r_amd.splatt3r_utils import splatt3r_render
+    _, depth, alpha = splatt3r_render(model, kf, kf, K=K, return_depth=True)
+    return torch.where(alpha >= alpha_min, depth / alpha, torch.zeros_like(depth)).contiguous()
+
+
+def eval_novel_view_renders(model, keyframes, K=None, gap=1, alpha_min=0.5):
+    """Score every keyframe i against the render of keyframe j = i - gap's
+    Gaussians from i's pose (splatt3r_render(model, kf_j, kf_j, K=K,
+    target_T_WC=kf_i.T_WC)), over the co-visibility mask the reference takes
+    its numbers over (loss_mask.calculate_in_frustum_mask; target view i,
+    context view j, depths rendered at each keyframe's own pose, poses the
+    4 x 4 (s R | t) of each T_WC, intrinsics the ones the render used).
+    Keyframes without Gaussian predictions on either side are skipped and
+    counted in `skipped`; pairs with an empty mask in `empty` (the reference
+    asserts mask.sum() > 0).  Returns a dict: `rows` (mse, psnr, ssim, l1,
+    `frame_id`, `source_id`, `mask_fraction`), `means`, `skipped`, `empty`."""
+    from splatt3r_amd.loss_mask import calculate_in_frustum_mask
+    from splatt3r_amd.photometric import image_metrics
+    from splatt3r_amd.splatt3r_utils import (_estimate_default_intrinsics, _sim3_to_4x4,
+                                             splatt3r_render)
+    has_pred = lambda kf: kf.gaussian_pred is not None and kf.gaussian_pred_cross is not None
+    rows, skipped, empty = [], 0, 0
+    for i in range(gap, len(keyframes)):
+        kf_i, kf_j = keyframes[i], keyframes[i - gap]
+        if not (has_pred(kf_i) and has_pred(kf_j)):
+            skipped += 1
+            continue
+        dev = kf_j.gaussian_pred["means"].device
+        _, h, w, _ = kf_j.gaussian_pred["means"].shape
+        K_use = (_estimate_default_intrinsics(h, w, dev) if K is None
+                 else K.detach().to(device=dev, dtype=torch.float32).reshape(-1, 3, 3)[0])
+        K_use = K_use.reshape(1, 1, 3, 3).contiguous()
+        render = splatt3r_render(model, kf_j, kf_j, K=K, target_T_WC=kf_i.T_WC)[0].contiguous()
+        pose = lambda kf: _sim3_to_4x4(kf.T_WC).to(dev).reshape(1, 1, 4, 4).contiguous()
+        mask = calculate_in_frustum_mask(_own_depth(model, kf_i, K, alpha_min), K_use, pose(kf_i),
+                                         _own_depth(model, kf_j, K, alpha_min), K_use, pose(kf_j),
+                                         as_float=True)[0]
+        fraction = float(mask.mean())
+        if fraction == 0.0:
+            empty += 1
+            continue
+        m = image_metrics(render, keyframe_target(kf_i).contiguous(), mask)
+        row = {k: float(v[0]) for k, v in m.items()}
+        row.update(frame_id=kf_i.frame_id, source_id=kf_j.frame_id, mask_fraction=fraction)
+        rows.append(row)
+    means = {k: float(np.mean([r[k] for r in rows])) for k in ("mse", "psnr", "ssim", "l1")} \
+        if rows else {}
+    return dict(rows=rows, means=means, skipped=skipped, empty=empty)
