@@ -85,6 +85,36 @@ int s3w_map_append(const s3w_map* map, const float* records, const int64_t* coun
 int s3w_map_scale(const float* means, const float* cov_triu, const int64_t* n_dev, int64_t n_max,
                   float s, float s2, float* means_out, float* cov_out, void* stream);
 
+/* ---- 3DGS splat rows (the .ply every 3DGS viewer and trainer reads) ----
+ * Export: one row of 17 floats per Gaussian, INRIA convention:
+ *   x y z            the mean, bit-exact
+ *   nx ny nz         0
+ *   f_dc_0..2        (colour - 0.5) / C0, C0 = 0.28209479177387814
+ *   opacity          logit(clamp(o, 1e-6, 1 - 1e-6))
+ *   scale_0..2       log(max(sqrt(max(lambda_i, 0)), scale_min)), lambda the
+ *                    eigenvalues of the covariance in descending order
+ *   rot_0..3         unit quaternion w x y z (the order gsr_preprocess reads
+ *                    `rotations` in), w >= 0, of the proper rotation whose
+ *                    columns are the eigenvectors in the order of the scales
+ *                    (a det -1 eigenvector matrix has its third column
+ *                    flipped).  Zero covariance: scale_min, (1, 0, 0, 0).
+ * Rows i < min(*n_dev, n_max) are written (n_dev NULL: n_max), the others are
+ * left untouched.  One thread per Gaussian, a fixed-sweep cyclic Jacobi on
+ * the matrix divided by its largest |entry|: a row is a pure function of its
+ * Gaussian's 10 inputs, bit-reproducible and independent of n.  `rows` must
+ * be 16-byte aligned.  Stream-ordered, no host sync. */
+int s3w_map_to_splats(const float* means, const float* cov_triu, const float* colors,
+                      const float* opacities, const int64_t* n_dev, int64_t n_max,
+                      float scale_min, float* rows, void* stream);
+
+/* Import: rows14 [n, 14] = x y z, f_dc_0..2, opacity, scale_0..2, rot_0..3
+ * (w x y z, normalised here) replace the map's content: means,
+ * cov_triu = R diag(exp(scale)^2) R^T, colors = clamp(f_dc C0 + 0.5, 0, 1),
+ * opacities = sigmoid(opacity), kf_id = kf_idx for rows [0, n), *map->n = n.
+ * n < 0 or n > cap returns S3_ERR_INVALID before any device work. */
+int s3w_map_from_splats(const s3w_map* map, const float* rows14, int64_t n, int32_t kf_idx,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,7 @@ SOURCES = {
     "ingest.hip": STRICT,
     "photometric.hip": STRICT,
     "loss_mask.hip": STRICT,
+    "splat_io.hip": STRICT,
 }
 
 

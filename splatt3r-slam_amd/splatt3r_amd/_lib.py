@@ -67,6 +67,9 @@ SIGNATURES: dict[str, tuple] = {
     # s3c.h
     "s3c_loss_mask_workspace_bytes": (SZ, [I32, I32, I32]),
     "s3c_loss_mask": (I32, [P, P, P, P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P]),
+    # s3w.h (splat rows; the map's other entries are registered by their modules)
+    "s3w_map_to_splats": (I32, [P, P, P, P, P, I64, F32, P, P]),
+    "s3w_map_from_splats": (I32, [P, P, I64, ctypes.c_int32, P]),
 }
 
 _lock = threading.Lock()

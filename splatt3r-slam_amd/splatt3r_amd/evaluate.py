@@ -24,6 +24,11 @@ camera images on the device (splatt3r_amd/photometric.py), and
 `eval_novel_view_renders` scores a keyframe against its neighbour's Gaussians
 over the co-visibility mask (splatt3r_amd/loss_mask.py).
 
+The Gaussian map itself leaves the process as a 3DGS splat file, which the
+reference's evaluate.py has no function for either: `write_splat_ply`,
+`read_splat_ply` and `save_gaussian_splats` (format and values: include/s3w.h
+s3w_map_to_splats).
+
 save_reconstruction's use_calib branch constrains points to their pixel
 rays first (evaluate.py:55-59).  save_traj's `intrinsics` branch calls
 `intrinsics.refine_pose_with_calibration(keyframe)` (evaluate.py:42), a
@@ -126,6 +131,118 @@ def save_reconstruction(savedir, filename, keyframes, c_conf_threshold):
         pts.append(pW[valid])
         cols.append(color[valid])
     save_ply(savedir / filename, np.concatenate(pts, 0), np.concatenate(cols, 0))
+
+
+# ------------------------------------------------------- 3DGS splat .ply ----
+# The file every 3DGS viewer and trainer reads (INRIA convention; the values
+# are defined in include/s3w.h s3w_map_to_splats).  Attribute list and order
+# as the reference's save_as_ply (splatt3r_core/utils/export.py) with the DC
+# band only; its arithmetic is not reproduced (it writes U @ U for the
+# rotation, scipy's x y z w order and post-sigmoid opacities).
+SPLAT_PROPERTIES = ("x", "y", "z", "nx", "ny", "nz", "f_dc_0", "f_dc_1", "f_dc_2", "opacity",
+                    "scale_0", "scale_1", "scale_2", "rot_0", "rot_1", "rot_2", "rot_3")
+# what an import needs (the normals are written as 0 and never read)
+SPLAT_REQUIRED = tuple(p for p in SPLAT_PROPERTIES if p not in ("nx", "ny", "nz"))
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2",
+              "int16": "i2", "ushort": "u2", "uint16": "u2", "int": "i4", "int32": "i4",
+              "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8",
+              "float64": "f8"}
+
+
+def splat_ply_header(n: int) -> str:
+    """The header plyfile writes for one vertex element of 17 float properties."""
+    return ("ply\nformat binary_little_endian 1.0\n" + f"element vertex {int(n)}\n"
+            + "".join(f"property float {p}\n" for p in SPLAT_PROPERTIES) + "end_header\n")
+
+
+def write_splat_ply(path, rows):
+    """Write a [n, 17] float32 array (columns in SPLAT_PROPERTIES order) as a
+    binary little-endian splat .ply: the header, then the rows as they are.
+    Host only; one write of the body."""
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or rows.shape[1] != len(SPLAT_PROPERTIES):
+        raise ValueError(f"write_splat_ply: rows must be [n, {len(SPLAT_PROPERTIES)}], "
+                         f"got {rows.shape}")
+    body = np.ascontiguousarray(rows, dtype="<f4")
+    with open(path, "wb") as f:
+        f.write(splat_ply_header(len(body)).encode("ascii"))
+        f.write(body.data)
+
+
+def read_splat_ply(path) -> dict:
+    """Read a 3DGS splat .ply into a dict of numpy arrays keyed by property
+    name (every vertex property of the file, each [n]).
+
+    Properties are found by name: any order, and extra ones (`f_rest_*` of a
+    file trained elsewhere, anything else) are accepted.  Only the DC band is
+    used on import; higher SH bands (`f_rest_*`) are returned here but ignored
+    by SharedGaussians.load_ply.  Raises ValueError for an ascii or big-endian
+    file, a missing or non-float required property (SPLAT_REQUIRED), and a
+    body shorter than the header promises."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    if not raw.startswith(b"ply"):
+        raise ValueError(f"{path}: not a PLY file")
+    end = raw.find(b"end_header\n")
+    if end < 0:
+        raise ValueError(f"{path}: PLY header has no end_header line")
+    body_at = end + len(b"end_header\n")
+    fmt, elements = None, []          # elements: [name, count, [(prop, dtype)]]
+    for line in raw[:end].decode("ascii", errors="replace").split("\n")[1:]:
+        tok = line.split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append([tok[1], int(tok[2]), []])
+        elif tok[0] == "property":
+            if not elements:
+                raise ValueError(f"{path}: property before any element")
+            if tok[1] == "list":
+                if elements[-1][0] == "vertex":
+                    raise ValueError(f"{path}: list property in the vertex element")
+                elements[-1][2] = None        # a variable-size element
+            elif elements[-1][2] is not None:
+                if tok[1] not in _PLY_TYPES:
+                    raise ValueError(f"{path}: unknown property type {tok[1]!r}")
+                elements[-1][2].append((tok[2], "<" + _PLY_TYPES[tok[1]]))
+    if fmt != "binary_little_endian":
+        raise ValueError(f"{path}: only binary_little_endian PLY is read, file is {fmt}")
+    offset, vertex = body_at, None
+    for name, count, props in elements:
+        if name == "vertex":
+            vertex = (count, props)
+            break
+        if props is None:
+            raise ValueError(f"{path}: a list element precedes the vertex element")
+        offset += count * np.dtype(props).itemsize
+    if vertex is None:
+        raise ValueError(f"{path}: no vertex element")
+    n, props = vertex
+    types = dict(props)
+    for p in SPLAT_REQUIRED:
+        if p not in types:
+            raise ValueError(f"{path}: missing property {p!r}")
+        if types[p] != "<f4":
+            raise ValueError(f"{path}: property {p!r} is not float")
+    dt = np.dtype(props)
+    if len(raw) - offset < n * dt.itemsize:
+        raise ValueError(f"{path}: truncated body ({len(raw) - offset} bytes for {n} vertices "
+                         f"of {dt.itemsize})")
+    rec = np.frombuffer(raw, dtype=dt, count=n, offset=offset)
+    return {name: np.ascontiguousarray(rec[name]) for name, _ in props}
+
+
+def save_gaussian_splats(savedir, filename, gmap):
+    """Write the Gaussian map as a splat .ply (SharedGaussians.save_ply) into
+    savedir, created like save_reconstruction does.  Returns the number of
+    Gaussians written, or None when there is no map or it is empty."""
+    if gmap is None or gmap.n_gaussians == 0:
+        return None
+    savedir = pathlib.Path(savedir)
+    savedir.mkdir(exist_ok=True, parents=True)
+    return gmap.save_ply(savedir / filename)
 
 
 def save_keyframes(savedir, timestamps, keyframes):

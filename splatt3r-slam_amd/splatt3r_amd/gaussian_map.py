@@ -113,6 +113,63 @@ class SharedGaussians:
     def clear(self):
         self._n.zero_()
 
+    # ---- 3DGS splat .ply (include/s3w.h, evaluate.write_splat_ply) ----
+    def to_splats(self, n: Optional[int] = None, scale_min: float = 1e-7) -> torch.Tensor:
+        """The first n Gaussians (default: all, a host read of the count) as
+        [n, 17] splat rows on the device.  With an explicit n there is no
+        host read; rows at and past the map's count are then left zero."""
+        if n is None:
+            n = self.n_gaussians
+            rows = torch.empty(n, 17, device=self.device)
+        else:
+            n = min(int(n), self.max_gaussians)
+            rows = torch.zeros(n, 17, device=self.device)
+        _lib.call("s3w_map_to_splats", self.means.data_ptr(), self.cov_triu.data_ptr(),
+                  self.colors.data_ptr(), self.opacities.data_ptr(), self._n.data_ptr(), n,
+                  float(scale_min), rows.data_ptr(), _lib.stream(self.device))
+        return rows
+
+    def save_ply(self, path) -> int:
+        """Write the map as a binary splat .ply: one kernel, one device-to-host
+        copy of the [n, 17] block, one file write.  Returns n."""
+        from splatt3r_amd.evaluate import write_splat_ply
+        rows = self.to_splats().cpu().numpy()
+        write_splat_ply(path, rows)
+        return len(rows)
+
+    def load_ply(self, path, kf_idx: int = -1) -> int:
+        """Replace the map's content by a splat .ply (this project's or one
+        trained elsewhere; DC colour only, `f_rest_*` ignored).  Every
+        Gaussian gets kf_id = kf_idx.  Raises ValueError, leaving the map
+        untouched, if the file holds more than max_gaussians.  Returns n."""
+        from splatt3r_amd.evaluate import SPLAT_REQUIRED, read_splat_ply
+        props = read_splat_ply(path)
+        rows14 = np.stack([props[p] for p in SPLAT_REQUIRED], 1).astype(np.float32)
+        n = len(rows14)
+        if n > self.max_gaussians:
+            raise ValueError(f"{path} holds {n} Gaussians, the map at most {self.max_gaussians}")
+        dev_rows = torch.from_numpy(np.ascontiguousarray(rows14)).to(self.device)
+        _lib.call("s3w_map_from_splats", ctypes.byref(self._c), dev_rows.data_ptr() if n else None,
+                  n, int(kf_idx), _lib.stream(self.device))
+        return n
+
+
+def splats_from_cov(means, cov_triu, colors, opacities, scale_min: float = 1e-7) -> torch.Tensor:
+    """[n, 17] splat rows (include/s3w.h s3w_map_to_splats) of n Gaussians
+    given as device tensors: means [n, 3], cov_triu [n, 6], colors [n, 3],
+    opacities [n] or [n, 1]."""
+    _lib.require_cuda(means, cov_triu, colors, opacities)
+    n = means.shape[0]
+    prep = lambda t, w: t.reshape(n, w).float().contiguous()
+    means, cov_triu, colors, opacities = (prep(means, 3), prep(cov_triu, 6), prep(colors, 3),
+                                          prep(opacities, 1))
+    rows = torch.empty(n, 17, device=means.device)
+    with torch.cuda.device(means.device):
+        _lib.call("s3w_map_to_splats", means.data_ptr(), cov_triu.data_ptr(), colors.data_ptr(),
+                  opacities.data_ptr(), None, n, float(scale_min), rows.data_ptr(),
+                  _lib.stream(means.device))
+    return rows
+
 
 def should_append_gaussians(add_new_kf: bool, frame_idx: int, current_T_WC,
                             last_append_T_WC, last_append_frame_idx: int,

@@ -30,6 +30,7 @@ from __future__ import annotations
 
 import contextlib
 import os
+import pathlib
 import queue
 import threading
 import time
@@ -410,6 +411,20 @@ class Frontend:
             if self._rworker.error is not None:
                 e, self._rworker.error = self._rworker.error, None
                 raise e
+
+    def save_map(self, path):
+        """Write the Gaussian map as a 3DGS splat .ply (evaluate.
+        save_gaussian_splats) once every queued render has been issued.
+        Returns the number of Gaussians written, or None when the session
+        keeps no map (viz off) or the map is empty."""
+        from splatt3r_amd.evaluate import save_gaussian_splats
+        self.drain()
+        path = pathlib.Path(path)
+        # on the stream the map's appends were issued on
+        st = self.main_stream if self.main_stream is not None else \
+            torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(st):
+            return save_gaussian_splats(path.parent, path.name, self.gmap)
 
     def close(self):
         """End the session: wait for queued renders, stop the render worker
