@@ -73,6 +73,7 @@ SOURCES = {
     "photometric.hip": STRICT,
     "loss_mask.hip": STRICT,
     "splat_io.hip": STRICT,
+    "splat_opt.hip": STRICT,
 }
 
 

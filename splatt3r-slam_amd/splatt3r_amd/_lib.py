@@ -70,6 +70,9 @@ SIGNATURES: dict[str, tuple] = {
     # s3w.h (splat rows; the map's other entries are registered by their modules)
     "s3w_map_to_splats": (I32, [P, P, P, P, P, I64, F32, P, P]),
     "s3w_map_from_splats": (I32, [P, P, I64, ctypes.c_int32, P]),
+    # s3o.h (hp: POINTER(refine.S3oAdam), passed with ctypes.byref)
+    "s3o_activate": (I32, [P, I64, F32, P, P, P, P, P, P]),
+    "s3o_adam_step": (I32, [P, P, P, I64, P, P, P, P, P, P, P, P, P]),
 }
 
 _lock = threading.Lock()

@@ -153,6 +153,36 @@ class SharedGaussians:
                   n, int(kf_idx), _lib.stream(self.device))
         return n
 
+    # ---- photometric refinement (include/s3o.h, splatt3r_amd.refine) ----
+    def refine(self, images, T_WC, K, iters, **kw):
+        """Fit the map to `images` ([V, 3, H, W] in [0, 1]) seen from `T_WC`
+        ([V, 4, 4] camera-to-world) with intrinsics `K`: to_splats,
+        refine.refine_splats (which takes **kw), s3w_map_from_splats.  The
+        count and every Gaussian's kf_id are kept.  A Gaussian whose row no
+        step touched (outside every view's frustum, with the default sparse
+        step) keeps its fields bit for bit: the row round trip is not
+        bit-exact, so its result is taken only where the row changed.
+        Returns the per-step losses (device tensor [iters]), or None for an
+        empty map."""
+        from splatt3r_amd.refine import refine_splats
+        n = self.n_gaussians
+        if n == 0:
+            return None
+        rows17 = self.to_splats(n)
+        before = torch.cat([rows17[:, :3], rows17[:, 6:]], 1).contiguous()
+        rows14, history = refine_splats(before, images, T_WC, K, iters, **kw)
+        changed = (rows14 != before).any(1)
+        fields = (self.means, self.cov_triu, self.colors, self.opacities, self.kf_id)
+        old = [f[:n].clone() for f in fields]
+        # s3w_map_from_splats overwrites kf_id
+        _lib.call("s3w_map_from_splats", ctypes.byref(self._c), rows14.data_ptr(), n, -1,
+                  _lib.stream(self.device))
+        for f, o in zip(fields[:4], old):
+            keep = changed if f.dim() == 1 else changed[:, None]
+            f[:n] = torch.where(keep, f[:n], o)
+        self.kf_id[:n] = old[4]
+        return history
+
 
 def splats_from_cov(means, cov_triu, colors, opacities, scale_min: float = 1e-7) -> torch.Tensor:
     """[n, 17] splat rows (include/s3w.h s3w_map_to_splats) of n Gaussians

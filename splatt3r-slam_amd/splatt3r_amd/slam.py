@@ -426,6 +426,33 @@ class Frontend:
         with torch.cuda.stream(st):
             return save_gaussian_splats(path.parent, path.name, self.gmap)
 
+    def refine_map(self, iters, **kw):
+        """Fit the Gaussian map to the keyframes' camera images
+        (SharedGaussians.refine) once every queued render has been issued:
+        image evaluate.keyframe_target(kf), pose the 4 x 4 (s R | t) of
+        kf.T_WC, intrinsics K or the default estimate, as
+        evaluate.eval_novel_view_renders takes them.  **kw goes to
+        refine.refine_splats.  Never called by the frame loop.  Returns the
+        per-step losses (device tensor), or None when the session keeps no
+        map (viz off), the map is empty or there is no keyframe."""
+        from splatt3r_amd.evaluate import keyframe_target
+        from splatt3r_amd.splatt3r_utils import _estimate_default_intrinsics
+        self.drain()
+        if self.gmap is None or len(self.keyframes) == 0:
+            return None
+        # on the stream the map's appends were issued on
+        st = self.main_stream if self.main_stream is not None else \
+            torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(st):
+            dev = self.gmap.device
+            kfs = [self.keyframes[i] for i in range(len(self.keyframes))]
+            images = torch.cat([keyframe_target(kf).to(dev) for kf in kfs]).contiguous()
+            poses = torch.cat([_sim3_to_4x4(kf.T_WC).to(dev).reshape(1, 4, 4) for kf in kfs])
+            h, w = images.shape[-2:]
+            K = (_estimate_default_intrinsics(h, w, "cpu") if self.K is None
+                 else self.K.detach().to("cpu", torch.float32).reshape(-1, 3, 3)[0])
+            return self.gmap.refine(images, poses, K, iters, **kw)
+
     def close(self):
         """End the session: wait for queued renders, stop the render worker
         thread and release the decode-ahead slot this session left on the
