@@ -74,6 +74,7 @@ SOURCES = {
     "loss_mask.hip": STRICT,
     "splat_io.hip": STRICT,
     "splat_opt.hip": STRICT,
+    "splat_density.hip": STRICT,
 }
 
 

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from splatt3r_amd import _lib
+from splatt3r_amd import refine as _refine  # noqa: F401  (registers the s3d.h entry points)
 
 
 class S3wMap(ctypes.Structure):
@@ -154,33 +155,55 @@ class SharedGaussians:
         return n
 
     # ---- photometric refinement (include/s3o.h, splatt3r_amd.refine) ----
-    def refine(self, images, T_WC, K, iters, **kw):
+    def refine(self, images, T_WC, K, iters, density=None, **kw):
         """Fit the map to `images` ([V, 3, H, W] in [0, 1]) seen from `T_WC`
         ([V, 4, 4] camera-to-world) with intrinsics `K`: to_splats,
-        refine.refine_splats (which takes **kw), s3w_map_from_splats.  The
-        count and every Gaussian's kf_id are kept.  A Gaussian whose row no
-        step touched (outside every view's frustum, with the default sparse
-        step) keeps its fields bit for bit: the row round trip is not
-        bit-exact, so its result is taken only where the row changed.
+        refine.refine_splats (which takes **kw), s3w_map_from_splats.
+
+        density None: the count and every Gaussian's kf_id are kept.  With a
+        refine.DensityControl (its capacity defaults to max_gaussians) the
+        passes prune, clone and split: the count becomes the number of rows
+        left, and every row takes the kf_id of the Gaussian density.origin
+        traces it to, so children inherit and, rows keeping their order, kf_id
+        stays non-decreasing where it was.
+
+        A surviving Gaussian whose row no step touched (outside every view's
+        frustum, with the default sparse step) keeps its fields bit for bit:
+        the row round trip is not bit-exact, so its result is taken only where
+        the row differs from the row it started as.
         Returns the per-step losses (device tensor [iters]), or None for an
         empty map."""
         from splatt3r_amd.refine import refine_splats
         n = self.n_gaussians
         if n == 0:
             return None
+        if density is not None:
+            if density.capacity is None:
+                density.capacity = self.max_gaussians
+            if density.capacity > self.max_gaussians:
+                raise ValueError(f"SharedGaussians.refine: density capacity {density.capacity} "
+                                 f"exceeds max_gaussians {self.max_gaussians}")
         rows17 = self.to_splats(n)
         before = torch.cat([rows17[:, :3], rows17[:, 6:]], 1).contiguous()
-        rows14, history = refine_splats(before, images, T_WC, K, iters, **kw)
-        changed = (rows14 != before).any(1)
+        rows14, history = refine_splats(before, images, T_WC, K, iters, density=density, **kw)
+        m = rows14.shape[0]
         fields = (self.means, self.cov_triu, self.colors, self.opacities, self.kf_id)
-        old = [f[:n].clone() for f in fields]
-        # s3w_map_from_splats overwrites kf_id
-        _lib.call("s3w_map_from_splats", ctypes.byref(self._c), rows14.data_ptr(), n, -1,
-                  _lib.stream(self.device))
+        if density is None:
+            changed = (rows14 != before).any(1)
+            old = [f[:n].clone() for f in fields]
+        else:
+            # the Gaussian each row started as (itself, or its ancestor)
+            origin = density.origin
+            src = torch.where(origin >= 0, origin, ~origin).long()
+            changed = (origin < 0) | (rows14 != before[src]).any(1)
+            old = [f[:n][src] for f in fields]
+        # s3w_map_from_splats overwrites kf_id and sets the count
+        _lib.call("s3w_map_from_splats", ctypes.byref(self._c), rows14.data_ptr() if m else None,
+                  m, -1, _lib.stream(self.device))
         for f, o in zip(fields[:4], old):
             keep = changed if f.dim() == 1 else changed[:, None]
-            f[:n] = torch.where(keep, f[:n], o)
-        self.kf_id[:n] = old[4]
+            f[:m] = torch.where(keep, f[:m], o)
+        self.kf_id[:m] = old[4]
         return history
 
 

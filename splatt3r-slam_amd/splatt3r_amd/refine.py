@@ -37,6 +37,27 @@ class S3oAdam(ctypes.Structure):
                 ("bias2_sqrt", ctypes.c_float), ("render_scale", ctypes.c_float)]
 
 
+class S3dParams(ctypes.Structure):
+    """s3d_params of include/s3d.h."""
+    _fields_ = [("grad_threshold", ctypes.c_float), ("split_scale", ctypes.c_float),
+                ("min_opacity", ctypes.c_float), ("max_scale", ctypes.c_float),
+                ("max_screen_radius", ctypes.c_int32), ("seed", ctypes.c_uint64),
+                ("pass_", ctypes.c_uint32)]
+
+
+_P = ctypes.c_void_p
+_lib.register({
+    # s3d.h (params: POINTER(S3dParams), passed with ctypes.byref)
+    "s3d_accumulate": (ctypes.c_int, [_P, _P, ctypes.c_int64, _P, _P, _P, _P]),
+    "s3d_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
+    "s3d_densify": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, _P, _P, _P, _P, ctypes.c_int64,
+                                   _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "s3d_reset_opacity": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, ctypes.c_float, _P]),
+})
+
+COUNTS = ("pruned", "cloned", "split", "denied")
+
+
 def _f32(x: float) -> float:
     return ctypes.c_float(float(x)).value
 
@@ -149,6 +170,266 @@ class SplatAdam:
                       *[p(g) for g in gs], None if radii is None else p(radii),
                       ctypes.byref(hp), self._skipped.data_ptr(), _lib.stream(dev))
 
+    @torch.no_grad()
+    def densify(self, stats, params, cap: int):
+        """One density pass (densify_splats) over the rows and both moment
+        arrays; the optimiser's three tensors are swapped for the results (new
+        rows start with zero moments, the step count is shared).  Returns
+        (origin, counts)."""
+        rows, m, v, origin, counts = densify_splats(self.rows14, self.exp_avg, self.exp_avg_sq,
+                                                    stats, params, cap)
+        self.rows14, self.exp_avg, self.exp_avg_sq = rows, m, v
+        return origin, counts
+
+    @torch.no_grad()
+    def reset_opacity(self, opacity: float = 0.01) -> None:
+        """3DGS's opacity reset: every logit becomes min(logit, logit(opacity))
+        and the opacity column of both moment arrays zero, in place."""
+        reset_opacity(self.rows14, self.exp_avg, self.exp_avg_sq, opacity)
+
+
+# ------------------------------------------------ density control (s3d.h) --
+def new_stats(n: int, device):
+    """Zeroed (grad_accum float32 [n], denom int32 [n], max_radii int32 [n])."""
+    return (torch.zeros(n, device=device, dtype=torch.float32),
+            torch.zeros(n, device=device, dtype=torch.int32),
+            torch.zeros(n, device=device, dtype=torch.int32))
+
+
+def _check_stats(stats, n, fn):
+    if len(stats) != 3:
+        raise ValueError(f"{fn}: stats must be (grad_accum, denom, max_radii)")
+    for t, dt, name in zip(stats, (torch.float32, torch.int32, torch.int32),
+                           ("grad_accum", "denom", "max_radii")):
+        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != (n,):
+            raise ValueError(f"{fn}: {name} must be a {dt} tensor of shape [{n}]")
+        _lib.require_cuda(t)
+        _lib.require_contig(fn, t)
+
+
+def as_params(params) -> S3dParams:
+    """An S3dParams from itself or from a mapping with the keys grad_threshold,
+    split_scale, min_opacity, max_scale, max_screen_radius, seed and pass (the
+    last four default to 0)."""
+    if isinstance(params, S3dParams):
+        return params
+    p = dict(params)
+    unknown = set(p) - {"grad_threshold", "split_scale", "min_opacity", "max_scale",
+                        "max_screen_radius", "seed", "pass"}
+    if unknown:
+        raise ValueError(f"density params: unknown keys {sorted(unknown)}")
+    vals = [float(p[k]) for k in ("grad_threshold", "split_scale", "min_opacity")]
+    vals.append(float(p.get("max_scale", 0.0)))
+    if any(math.isnan(v) for v in vals):
+        raise ValueError("density params: a threshold is NaN")
+    seed, pass_ = int(p.get("seed", 0)), int(p.get("pass", 0))
+    if not (0 <= seed < 2 ** 64 and 0 <= pass_ < 2 ** 32):
+        raise ValueError("density params: seed must fit 64 bits and pass 32, unsigned")
+    return S3dParams(*vals, int(p.get("max_screen_radius", 0)), seed, pass_)
+
+
+@torch.no_grad()
+def accumulate_stats(d_means2D: torch.Tensor, radii: torch.Tensor, stats) -> None:
+    """Add one step to the density statistics (include/s3d.h s3d_accumulate):
+    d_means2D [n, 3] is the gradient the rasterizer's backward leaves on its
+    means2D argument, radii [n] the same forward's int32 radii."""
+    n = radii.shape[0]
+    if d_means2D.dtype != torch.float32 or tuple(d_means2D.shape) != (n, 3):
+        raise ValueError(f"accumulate_stats: d_means2D must be float32 [{n}, 3]")
+    if radii.dtype != torch.int32 or radii.dim() != 1:
+        raise ValueError("accumulate_stats: radii must be int32 [n]")
+    _check_stats(stats, n, "accumulate_stats")
+    _lib.require_cuda(d_means2D, radii)
+    d_means2D, radii = d_means2D.contiguous(), radii.contiguous()
+    if n == 0:
+        return
+    with torch.cuda.device(radii.device):
+        _lib.call("s3d_accumulate", d_means2D.data_ptr(), radii.data_ptr(), n,
+                  *[t.data_ptr() for t in stats], _lib.stream(radii.device))
+
+
+@torch.no_grad()
+def densify_splats(rows14, exp_avg, exp_avg_sq, stats, params, cap: int):
+    """One density pass (include/s3d.h s3d_densify): prune, clone and split
+    the rows and their two Adam moment arrays, out of place.  stats:
+    (grad_accum, denom, max_radii); params: an S3dParams or a mapping
+    (as_params); cap: the most rows the result may have, >= n.
+
+    Returns (rows14, exp_avg, exp_avg_sq, origin, counts): the three [n_out,
+    14] arrays, origin int32 [n_out] (i for a kept row or a clone's original,
+    ~i for a clone's copy or a split child) and counts, a dict of pruned,
+    cloned, split and denied.  One host read: n_out and the counts, in one
+    copy."""
+    _check_rows(rows14, "densify_splats")
+    n = rows14.shape[0]
+    dev = rows14.device
+    for t, name in ((exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (n, 14):
+            raise ValueError(f"densify_splats: {name} must be float32 [{n}, 14]")
+        _lib.require_cuda(t)
+        _lib.require_contig("densify_splats", t)
+    _check_stats(stats, n, "densify_splats")
+    hp = as_params(params)
+    cap = int(cap)
+    if cap < n:
+        raise ValueError(f"densify_splats: cap {cap} < n {n}")
+    # no row has more than two outputs, so a capacity past 2 n never binds
+    cap = min(cap, 2 * n)
+    e = lambda: torch.empty(cap, 14, device=dev, dtype=torch.float32)
+    out = e(), e(), e()
+    origin = torch.empty(cap, device=dev, dtype=torch.int32)
+    if n == 0:
+        return (*out, origin, dict.fromkeys(COUNTS, 0))
+    # n_out (int64) and the four int32 counts share one buffer: one host read
+    tally = torch.zeros(3, device=dev, dtype=torch.int64)
+    with torch.cuda.device(dev):
+        need = int(_lib.lib().s3d_workspace_bytes(n))
+        ws = torch.empty(need, device=dev, dtype=torch.uint8)
+        _lib.call("s3d_densify", rows14.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n,
+                  *[t.data_ptr() for t in stats], ctypes.byref(hp), cap,
+                  *[t.data_ptr() for t in out], origin.data_ptr(), tally.data_ptr(),
+                  tally.data_ptr() + 8, ws.data_ptr(), need, _lib.stream(dev))
+    host = tally.cpu()
+    n_out = int(host[0])
+    counts = dict(zip(COUNTS, host[1:].view(torch.int32).tolist()))
+    return (*[t[:n_out] for t in out], origin[:n_out], counts)
+
+
+@torch.no_grad()
+def reset_opacity(rows14, exp_avg, exp_avg_sq, opacity: float = 0.01) -> None:
+    """include/s3d.h s3d_reset_opacity, in place; the cap logit(opacity) is
+    computed in double and rounded to float32 once."""
+    _check_rows(rows14, "reset_opacity")
+    n = rows14.shape[0]
+    for t in (exp_avg, exp_avg_sq):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (n, 14):
+            raise ValueError(f"reset_opacity: the moment arrays must be float32 [{n}, 14]")
+        _lib.require_cuda(t)
+        _lib.require_contig("reset_opacity", t)
+    if not 0.0 < float(opacity) < 1.0:
+        raise ValueError(f"reset_opacity: opacity must be in (0, 1), got {opacity}")
+    cap = math.log(float(opacity) / (1.0 - float(opacity)))
+    if n == 0:
+        return
+    with torch.cuda.device(rows14.device):
+        _lib.call("s3d_reset_opacity", rows14.data_ptr(), exp_avg.data_ptr(),
+                  exp_avg_sq.data_ptr(), n, cap, _lib.stream(rows14.device))
+
+
+def compose_origin(prev: torch.Tensor, origin: torch.Tensor) -> torch.Tensor:
+    """`origin` of one pass, whose inputs had the composed origin `prev`,
+    composed down to the rows prev refers to: i for a row that is input row i
+    itself, ~i for a row created since, out of input row i."""
+    src = torch.where(origin >= 0, origin, ~origin).long()
+    base = prev[src]
+    return torch.where((origin < 0) & (base >= 0), ~base, base)
+
+
+class DensityControl:
+    """Adaptive density control of refine_splats: INRIA 3DGS's
+    densify_and_prune and reset_opacity as include/s3d.h restates them.
+
+    After step t (counted from 1) a pass runs when start <= t <= stop and
+    t % interval == 0; the opacities are reset after a step with
+    t % opacity_reset_interval == 0 (0: never).  Between passes every step's
+    dL/dmeans2D and radii go into the statistics (s3d_accumulate); a pass
+    zeroes them at the new size.
+
+    grad_threshold, percent_dense, min_opacity and the schedule are 3DGS's
+    defaults.  Nobody has tuned them for this map: 3DGS runs 30,000 steps over
+    a whole scene, this map is refined for far fewer against a few keyframes.
+    A growing row splits when its largest scale exceeds percent_dense x extent
+    and is pruned when it exceeds max_world_scale x extent (0: never) or when
+    its largest screen radius exceeded max_screen_radius pixels (0: never).
+    extent None: 1.1 x the largest distance of a camera centre from the
+    centres' mean, as 3DGS's cameras_extent; ValueError if that is 0 (one
+    view, or coincident cameras).  capacity None: no row limit but the two
+    outputs per row (SharedGaussians.refine sets max_gaussians).
+
+    After a run: .log holds one dict per pass (t, n before, the four counts,
+    n_out); .origin maps every final row to the run's first input (i: that
+    row itself; ~i: created during the run, out of row i).
+    on_pass(pass_index, inputs, outputs), for tests: inputs = (rows14,
+    exp_avg, exp_avg_sq, grad_accum, denom, max_radii, params, cap), outputs
+    = (rows14, exp_avg, exp_avg_sq, origin, counts)."""
+
+    def __init__(self, start: int = 500, interval: int = 100, stop: int = 15000,
+                 grad_threshold: float = 2e-4, percent_dense: float = 0.01, extent=None,
+                 min_opacity: float = 0.005, max_world_scale: float = 0.1,
+                 max_screen_radius: int = 0, opacity_reset_interval: int = 0, capacity=None,
+                 seed: int = 0, on_pass=None):
+        self.start, self.interval, self.stop = int(start), int(interval), int(stop)
+        if self.start < 0 or self.interval < 1 or self.stop < self.start:
+            raise ValueError("DensityControl: need start >= 0, interval >= 1, stop >= start")
+        vals = dict(grad_threshold=grad_threshold, percent_dense=percent_dense,
+                    min_opacity=min_opacity, max_world_scale=max_world_scale)
+        for k, v in vals.items():
+            if not (float(v) >= 0.0 and math.isfinite(float(v))):
+                raise ValueError(f"DensityControl: {k} must be >= 0 and finite, got {v}")
+        self.grad_threshold, self.percent_dense = float(grad_threshold), float(percent_dense)
+        self.min_opacity, self.max_world_scale = float(min_opacity), float(max_world_scale)
+        if extent is not None and not (float(extent) > 0.0 and math.isfinite(float(extent))):
+            raise ValueError(f"DensityControl: extent must be > 0 and finite, got {extent}")
+        self.extent = None if extent is None else float(extent)
+        self.max_screen_radius = int(max_screen_radius)
+        self.opacity_reset_interval = int(opacity_reset_interval)
+        if self.max_screen_radius < 0 or self.opacity_reset_interval < 0:
+            raise ValueError("DensityControl: max_screen_radius and opacity_reset_interval "
+                             "must be >= 0")
+        if capacity is not None and int(capacity) < 0:
+            raise ValueError("DensityControl: capacity must be >= 0")
+        self.capacity = None if capacity is None else int(capacity)
+        self.seed = int(seed)
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError("DensityControl: seed must fit 64 bits, unsigned")
+        self.on_pass = on_pass
+        self.log: list = []
+        self.origin: Optional[torch.Tensor] = None
+
+    @staticmethod
+    def cameras_extent(T_WC) -> float:
+        """1.1 x the largest distance of a camera centre from the centres' mean."""
+        c = T_WC.detach().to("cpu", torch.float64)[:, :3, 3]
+        return 1.1 * float((c - c.mean(0, keepdim=True)).norm(dim=1).max())
+
+    def due(self, t: int) -> bool:
+        return self.start <= t <= self.stop and t % self.interval == 0
+
+    def reset_due(self, t: int) -> bool:
+        return self.opacity_reset_interval > 0 and t % self.opacity_reset_interval == 0
+
+    def begin(self, n: int, T_WC, device) -> None:
+        """Start a run over n rows seen from the poses T_WC."""
+        extent = self.extent if self.extent is not None else self.cameras_extent(T_WC)
+        if not extent > 0.0:
+            raise ValueError("DensityControl: the camera centres coincide, so the scene extent "
+                             "is 0; pass extent=")
+        if self.capacity is not None and self.capacity < n:
+            raise ValueError(f"DensityControl: capacity {self.capacity} < {n} rows")
+        self._extent = extent
+        self.log = []
+        self.origin = torch.arange(n, device=device, dtype=torch.int32)
+
+    def params(self, pass_index: int) -> S3dParams:
+        return S3dParams(self.grad_threshold, self.percent_dense * self._extent, self.min_opacity,
+                         self.max_world_scale * self._extent, self.max_screen_radius, self.seed,
+                         int(pass_index))
+
+    def run_pass(self, opt: "SplatAdam", stats, t: int):
+        """One pass on the optimiser's tensors; returns the zeroed statistics
+        of the new size."""
+        k = len(self.log)
+        n = opt.rows14.shape[0]
+        hp = self.params(k)
+        cap = 2 * n if self.capacity is None else self.capacity
+        inputs = (opt.rows14, opt.exp_avg, opt.exp_avg_sq, *stats, hp, cap)
+        origin, counts = opt.densify(stats, hp, cap)
+        self.origin = compose_origin(self.origin, origin)
+        self.log.append(dict(t=t, n=n, **counts, n_out=opt.rows14.shape[0]))
+        if self.on_pass is not None:
+            self.on_pass(k, inputs, (opt.rows14, opt.exp_avg, opt.exp_avg_sq, origin, counts))
+        return new_stats(opt.rows14.shape[0], opt.rows14.device)
+
 
 def _cameras(T_WC, K, H, W, near, far, bg, dev):
     """render.camera_settings (scale-invariant) of V camera-to-world poses:
@@ -182,7 +463,8 @@ def render_splats(rows14, T_WC, K, H, W, near=0.1, far=1000.0, bg=None):
 
 
 def refine_splats(rows14, images, T_WC, K, iters, masks=None, l1_weight=0.8, ssim_weight=0.2,
-                  mse_weight=0.0, near=0.1, far=1000.0, bg=None, sparse=True, order=None, **lr):
+                  mse_weight=0.0, near=0.1, far=1000.0, bg=None, sparse=True, order=None,
+                  density=None, **lr):
     """Fit splat rows to images.  rows14 [n, 14] float32 on the GPU (a copy is
     refined; the argument is left as it is), images [V, 3, H, W] in [0, 1],
     T_WC [V, 4, 4] camera-to-world, K [3, 3] pixel intrinsics, masks
@@ -193,10 +475,16 @@ def refine_splats(rows14, images, T_WC, K, iters, masks=None, l1_weight=0.8, ssi
     photometric_loss -> one backward -> one fused SplatAdam step, on that
     forward's radii when `sparse`.  **lr: SplatAdam's keyword arguments.
 
+    density: a DensityControl, or None for a fixed set of Gaussians.  With
+    one, means2D carries a gradient, every step's dL/dmeans2D and radii go to
+    s3d_accumulate, and a pass (prune, clone, split) runs when due: the number
+    of rows then changes, density.origin maps the returned rows to the rows
+    given, and each pass reads its row count back (one host read).
+
     Returns (rows14, history): the refined rows and the per-step losses
-    [iters] as a device tensor (the loss before each step).  The loop itself
-    reads nothing back from the device (the rasterizer's forward reads its
-    instance count, as in every differentiable render)."""
+    [iters] as a device tensor (the loss before each step).  Without density
+    the loop itself reads nothing back from the device (the rasterizer's
+    forward reads its instance count, as in every differentiable render)."""
     from diff_gaussian_rasterization import GaussianRasterizer
     from splatt3r_amd.photometric import photometric_loss
     _check_rows(rows14, "refine_splats")
@@ -216,16 +504,24 @@ def refine_splats(rows14, images, T_WC, K, iters, masks=None, l1_weight=0.8, ssi
     rows = rows14.detach().clone()
     opt = SplatAdam(rows, **lr)
     history = torch.zeros(int(iters), device=dev, dtype=torch.float32)
+    if density is not None:
+        if not isinstance(density, DensityControl):
+            raise TypeError("refine_splats: density must be a DensityControl or None")
+        density.begin(rows.shape[0], T_WC, dev)
     if int(iters) == 0 or rows.shape[0] == 0:
         return rows, history
     with torch.cuda.device(dev):
         settings, s = _cameras(T_WC, K, H, W, near, far, bg, dev)
+        stats = None if density is None else new_stats(rows.shape[0], dev)
         for it in range(int(iters)):
             v = order[it % len(order)]
-            acts = [t.requires_grad_(True) for t in activate(rows, s)]
+            acts = [t.requires_grad_(True) for t in activate(opt.rows14, s)]
             means3D, shs, opac, scales, rots = acts
+            means2D = torch.zeros_like(means3D)
+            if density is not None:
+                means2D.requires_grad_(True)
             img, radii = GaussianRasterizer(settings[v])(
-                means3D=means3D, means2D=torch.zeros_like(means3D), opacities=opac, shs=shs,
+                means3D=means3D, means2D=means2D, opacities=opac, shs=shs,
                 scales=scales, rotations=rots)
             loss = photometric_loss(img[None], images[v:v + 1],
                                     None if masks is None else masks[v:v + 1],
@@ -234,4 +530,13 @@ def refine_splats(rows14, images, T_WC, K, iters, masks=None, l1_weight=0.8, ssi
             loss.backward()
             history[it] = loss.detach()
             opt.step([a.grad for a in acts], radii if sparse else None, s)
-    return rows, history
+            if density is None:
+                continue
+            accumulate_stats(means2D.grad, radii, stats)
+            if density.due(it + 1):
+                stats = density.run_pass(opt, stats, it + 1)
+                if opt.rows14.shape[0] == 0:      # every row pruned: nothing left to fit
+                    break
+            if density.reset_due(it + 1):
+                opt.reset_opacity()
+    return opt.rows14, history
