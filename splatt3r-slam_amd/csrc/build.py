@@ -75,6 +75,7 @@ SOURCES = {
     "splat_io.hip": STRICT,
     "splat_opt.hip": STRICT,
     "splat_density.hip": STRICT,
+    "pose_grad.hip": STRICT,
 }
 
 

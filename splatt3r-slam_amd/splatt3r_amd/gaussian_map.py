@@ -206,6 +206,29 @@ class SharedGaussians:
         self.kf_id[:m] = old[4]
         return history
 
+    def refine_pose(self, image, T_WC, K, iters, near: float = 0.1, **kw):
+        """Localise one view against the map: fit the camera-to-world pose
+        `T_WC` [4, 4] to `image` ([3, H, W] in [0, 1]) with intrinsics `K`,
+        the map rendered as render_map feeds the rasterizer (s3w_map_scale,
+        cov3D_precomp, colors_precomp) and the pose gradient taken in its
+        covariance form (refine.localise, which takes **kw: poses, mask, the
+        loss weights, far, bg).  The map is read only: its five fields keep
+        their bits.  Returns (T_WC float64 [4, 4] on the device, the per-step
+        losses [iters]), or None for an empty map."""
+        from splatt3r_amd.refine import localise
+        n = self.n_gaussians
+        if n == 0:
+            return None
+        s = float(1 / torch.full((1,), float(near)))   # camera_settings' float32 factor
+        sc_means = torch.empty(n, 3, device=self.device)
+        sc_cov = torch.empty(n, 6, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.call("s3w_map_scale", self.means.data_ptr(), self.cov_triu.data_ptr(),
+                      self._n.data_ptr(), n, s, s * s, sc_means.data_ptr(), sc_cov.data_ptr(),
+                      _lib.stream(self.device))
+        return localise(sc_means, sc_cov, self.colors[:n], self.opacities[:n, None], image, T_WC, K,
+                        iters, near=near, **kw)
+
 
 def splats_from_cov(means, cov_triu, colors, opacities, scale_min: float = 1e-7) -> torch.Tensor:
     """[n, 17] splat rows (include/s3w.h s3w_map_to_splats) of n Gaussians

@@ -8,6 +8,12 @@
                  not touch
   refine_splats  the loop: activate, render, photometric loss, backward, step
   render_splats  the images that loop compares against its targets
+  pose_gradient  dL/dpose of one view, reduced from the rasterizer's
+                 per-Gaussian gradients (include/s3x.h, csrc/pose_grad.hip)
+  PoseControl    Adam on the camera twists, fused with the retraction and the
+                 camera rewrite (one HIP launch per step, k_pose_step)
+  refine_poses   the loop with the map fixed and only the poses moving;
+                 localise: the same for one view of cov3D_precomp Gaussians
 
 The reference has no counterpart (its training optimises network weights,
 never Gaussians).  The parametrisation is INRIA 3DGS's, which the project's
@@ -45,7 +51,19 @@ class S3dParams(ctypes.Structure):
                 ("pass_", ctypes.c_uint32)]
 
 
+class S3xPoseAdam(ctypes.Structure):
+    """s3x_pose_adam of include/s3x.h."""
+    _fields_ = [(k, ctypes.c_double) for k in ("lr_translation", "lr_rotation", "beta1", "beta2",
+                                               "eps", "bias1", "bias2_sqrt", "render_scale")]
+
+
 _P = ctypes.c_void_p
+_lib.register({
+    # s3x.h (hp: POINTER(S3xPoseAdam), passed with ctypes.byref)
+    "s3x_pose_grad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
+    "s3x_pose_grad": (ctypes.c_int, [_P] * 8 + [ctypes.c_int64, _P, _P, _P, ctypes.c_size_t, _P]),
+    "s3x_pose_step": (ctypes.c_int, [_P] * 10),
+})
 _lib.register({
     # s3d.h (params: POINTER(S3dParams), passed with ctypes.byref)
     "s3d_accumulate": (ctypes.c_int, [_P, _P, ctypes.c_int64, _P, _P, _P, _P]),
@@ -464,7 +482,7 @@ def render_splats(rows14, T_WC, K, H, W, near=0.1, far=1000.0, bg=None):
 
 def refine_splats(rows14, images, T_WC, K, iters, masks=None, l1_weight=0.8, ssim_weight=0.2,
                   mse_weight=0.0, near=0.1, far=1000.0, bg=None, sparse=True, order=None,
-                  density=None, **lr):
+                  density=None, poses=None, **lr):
     """Fit splat rows to images.  rows14 [n, 14] float32 on the GPU (a copy is
     refined; the argument is left as it is), images [V, 3, H, W] in [0, 1],
     T_WC [V, 4, 4] camera-to-world, K [3, 3] pixel intrinsics, masks
@@ -480,6 +498,14 @@ def refine_splats(rows14, images, T_WC, K, iters, masks=None, l1_weight=0.8, ssi
     s3d_accumulate, and a pass (prune, clone, split) runs when due: the number
     of rows then changes, density.origin maps the returned rows to the rows
     given, and each pass reads its row count back (one host read).
+
+    poses: a PoseControl, or None for poses taken as exact (the same launches
+    and the same bits as before the argument existed).  With one, the cameras
+    live on the device in float64, every step also reduces that backward's
+    gradients to dL/dpose (pose_gradient, rotation form) and steps the view
+    just rendered (s3x_pose_step) unless it is in poses.fixed; the refined
+    poses are poses.T_WC.  Rows and poses together have a 6-dof gauge: fix a
+    view, PoseControl(fixed=(0,)).
 
     Returns (rows14, history): the refined rows and the per-step losses
     [iters] as a device tensor (the loss before each step).  Without density
@@ -508,10 +534,18 @@ def refine_splats(rows14, images, T_WC, K, iters, masks=None, l1_weight=0.8, ssi
         if not isinstance(density, DensityControl):
             raise TypeError("refine_splats: density must be a DensityControl or None")
         density.begin(rows.shape[0], T_WC, dev)
+    if poses is not None and not isinstance(poses, PoseControl):
+        raise TypeError("refine_splats: poses must be a PoseControl or None")
     if int(iters) == 0 or rows.shape[0] == 0:
+        if poses is not None:
+            with torch.cuda.device(dev):
+                _pose_cameras(poses, T_WC, K, H, W, near, far, bg, dev)
         return rows, history
     with torch.cuda.device(dev):
-        settings, s = _cameras(T_WC, K, H, W, near, far, bg, dev)
+        if poses is None:
+            settings, s = _cameras(T_WC, K, H, W, near, far, bg, dev)
+        else:
+            settings, s = _pose_cameras(poses, T_WC, K, H, W, near, far, bg, dev)
         stats = None if density is None else new_stats(rows.shape[0], dev)
         for it in range(int(iters)):
             v = order[it % len(order)]
@@ -529,7 +563,14 @@ def refine_splats(rows14, images, T_WC, K, iters, masks=None, l1_weight=0.8, ssi
                                     ssim_weight=ssim_weight)
             loss.backward()
             history[it] = loss.detach()
+            if poses is not None and v not in poses.fixed:
+                # on the view matrix this forward and backward used
+                g = pose_gradient(settings[v].viewmatrix, means3D.detach(), means3D.grad,
+                                  rotations=rots.detach(), d_rotations=rots.grad, radii=radii,
+                                  skipped=poses._skipped)
             opt.step([a.grad for a in acts], radii if sparse else None, s)
+            if poses is not None and v not in poses.fixed:
+                poses.step(v, g)
             if density is None:
                 continue
             accumulate_stats(means2D.grad, radii, stats)
@@ -540,3 +581,322 @@ def refine_splats(rows14, images, T_WC, K, iters, masks=None, l1_weight=0.8, ssi
             if density.reset_due(it + 1):
                 opt.reset_opacity()
     return opt.rows14, history
+
+
+# --------------------------------------------- pose refinement (s3x.h) ----
+def _check_f32(fn, n, width, tensors, names):
+    for t, name in zip(tensors, names):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.numel() != n * width:
+            raise ValueError(f"{fn}: {name} must be a float32 tensor of {n} x {width} entries")
+
+
+def _rows_of(t, n, width):
+    t = t.detach().reshape(n, width).contiguous()
+    # a view into a wider tensor may start off the 16 bytes a float4 row needs
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+@torch.no_grad()
+def pose_gradient(viewmatrix, means3D, d_means3D, *, cov3D=None, d_cov3D=None, rotations=None,
+                  d_rotations=None, radii=None, skipped=None):
+    """dL/dxi of one view, a float64 [6] device tensor (include/s3x.h
+    s3x_pose_grad): xi = (rho, phi) is the twist of T_WC <- T_WC Exp(xi), in
+    the camera's own frame and in view-space units, reduced from the
+    gradients GaussianRasterizer's backward leaves on means3D and on either
+    cov3D_precomp (cov3D, d_cov3D [n, 6]) or rotations (rotations,
+    d_rotations [n, 4], unit quaternions as activate() writes them, with
+    scale_modifier-independent scales).  viewmatrix: the [4, 4] device view
+    matrix of that forward.  radii: the forward's int32 [n] (rows with
+    radii <= 0 are not loaded) or None for every row.  skipped: a device
+    int32 [1] counter, added to for every row left out because an input was
+    not finite.
+
+    Valid for SH degree 0 or colors_precomp only: with SH degree > 0 the
+    colour depends on the view direction and this is not the whole gradient.
+    Bit-reproducible: the same inputs give the same six doubles."""
+    fn = "pose_gradient"
+    if (cov3D is None) != (d_cov3D is None) or (rotations is None) != (d_rotations is None):
+        raise ValueError(f"{fn}: cov3D goes with d_cov3D, rotations with d_rotations")
+    if (cov3D is None) == (rotations is None):
+        raise ValueError(f"{fn}: give either cov3D and d_cov3D or rotations and d_rotations")
+    if not torch.is_tensor(means3D) or means3D.dim() != 2 or means3D.shape[1] != 3:
+        raise ValueError(f"{fn}: means3D must be [n, 3]")
+    n = means3D.shape[0]
+    _check_f32(fn, n, 3, (means3D, d_means3D), ("means3D", "d_means3D"))
+    if cov3D is not None:
+        width, shape = 6, (cov3D, d_cov3D)
+        _check_f32(fn, n, 6, shape, ("cov3D", "d_cov3D"))
+    else:
+        width, shape = 4, (rotations, d_rotations)
+        _check_f32(fn, n, 4, shape, ("rotations", "d_rotations"))
+    if not torch.is_tensor(viewmatrix) or viewmatrix.numel() != 16:
+        raise ValueError(f"{fn}: viewmatrix must hold 4 x 4 entries")
+    if radii is not None and (not torch.is_tensor(radii) or radii.dtype != torch.int32
+                              or tuple(radii.shape) != (n,)):
+        raise ValueError(f"{fn}: radii must be int32 [{n}]")
+    if skipped is not None and (not torch.is_tensor(skipped) or skipped.dtype != torch.int32
+                                or skipped.numel() != 1):
+        raise ValueError(f"{fn}: skipped must be an int32 tensor of one entry")
+    _lib.require_cuda(viewmatrix, means3D, d_means3D, *shape, radii, skipped)
+    mu, dmu = _rows_of(means3D, n, 3), _rows_of(d_means3D, n, 3)
+    sh, dsh = _rows_of(shape[0], n, width), _rows_of(shape[1], n, width)
+    radii = None if radii is None else radii.contiguous()
+    dev = mu.device
+    vm = viewmatrix.detach().to(torch.float32).contiguous()
+    out = torch.empty(6, device=dev, dtype=torch.float64)
+    p = lambda t: t.data_ptr() if n else None
+    # which pair is non-null names the form, also for n == 0 (nothing is read then)
+    pair = (sh.data_ptr() or 16, dsh.data_ptr() or 16)
+    with torch.cuda.device(dev):
+        need = int(_lib.lib().s3x_pose_grad_workspace_bytes(n))
+        ws = torch.empty(need // 8, device=dev, dtype=torch.float64)
+        _lib.call("s3x_pose_grad", vm.data_ptr(), p(mu), p(dmu),
+                  *(pair if cov3D is not None else (None, None)),
+                  *(pair if cov3D is None else (None, None)),
+                  None if radii is None else p(radii), n, out.data_ptr(),
+                  None if skipped is None else skipped.data_ptr(), ws.data_ptr(), need,
+                  _lib.stream(dev))
+    return out
+
+
+class PoseControl:
+    """Camera poses as optimisation variables of refine_splats, refine_poses
+    and SharedGaussians.refine_pose: Adam on the six components of the twist
+    xi = (rho, phi) of T_WC <- T_WC Exp(xi) (the camera's own frame), one
+    moment pair per view, fused with the retraction and the rewrite of that
+    view's float32 camera (include/s3x.h s3x_pose_step).
+
+    The learning rates are MonoGS's (rotation 3e-3, translation 1e-3).  Nobody
+    has tuned them for this map.  `fixed` names the views that are never
+    stepped.  Gaussians and poses refined together have a 6-dof gauge (a rigid
+    motion of everything changes no image): pass fixed=(0,) there.
+
+    After a run: .T_WC is the float64 [V, 4, 4] device tensor of the refined
+    camera-to-world poses (a fixed view's is its input, bit for bit; a uniform
+    scale of the 3 x 3 block is kept), .skipped the number of Gaussian rows
+    the gradient left out because an input was not finite (a host read of the
+    device counter).  A step whose gradient holds a NaN or an Inf leaves that
+    pose and its moments as they were.  Writing the poses back into keyframes
+    or the factor graph is the caller's business."""
+
+    def __init__(self, lr_rotation: float = 3e-3, lr_translation: float = 1e-3,
+                 betas=(0.9, 0.999), eps: float = 1e-15, fixed=()):
+        self.lr_rotation, self.lr_translation = float(lr_rotation), float(lr_translation)
+        self.betas = (float(betas[0]), float(betas[1]))
+        self.eps = float(eps)
+        for k, v in (("lr_rotation", self.lr_rotation), ("lr_translation", self.lr_translation)):
+            if not (v >= 0.0 and math.isfinite(v)):
+                raise ValueError(f"PoseControl: {k} must be >= 0 and finite, got {v}")
+        if not all(0.0 <= b < 1.0 for b in self.betas):
+            raise ValueError(f"PoseControl: betas must be in [0, 1), got {self.betas}")
+        if not (self.eps > 0.0 and math.isfinite(self.eps)):
+            raise ValueError(f"PoseControl: eps must be > 0 and finite, got {eps}")
+        self.fixed = tuple(sorted({int(v) for v in fixed}))
+        if any(v < 0 for v in self.fixed):
+            raise ValueError(f"PoseControl: fixed must name views by index >= 0, got {fixed}")
+        self.T_WC: Optional[torch.Tensor] = None
+        self._skipped: Optional[torch.Tensor] = None
+
+    @property
+    def skipped(self) -> int:
+        return 0 if self._skipped is None else int(self._skipped.item())
+
+    def begin(self, T_WC, proj_t, render_scale: float, device) -> None:
+        """Start a run from the poses T_WC [V, 4, 4]: the state moves to the
+        device and every view's camera is written.  proj_t: the transposed
+        projection matrix [4, 4]."""
+        if not torch.is_tensor(T_WC) or T_WC.dim() != 3 or tuple(T_WC.shape[1:]) != (4, 4):
+            raise ValueError("PoseControl: T_WC must be [V, 4, 4]")
+        V = T_WC.shape[0]
+        if any(v >= V for v in self.fixed):
+            raise ValueError(f"PoseControl: fixed {self.fixed} must index the {V} views")
+        if not (float(render_scale) > 0.0 and math.isfinite(float(render_scale))):
+            raise ValueError("PoseControl: render_scale must be > 0 and finite")
+        dev = torch.device(device)
+        _lib.require_cuda(torch.empty(0, device=dev))
+        self.T_WC = T_WC.detach().to(dev, torch.float64).contiguous().clone()
+        self.exp_avg = torch.zeros(V, 6, device=dev, dtype=torch.float64)
+        self.exp_avg_sq = torch.zeros(V, 6, device=dev, dtype=torch.float64)
+        self.cameras = torch.empty(V, 35, device=dev, dtype=torch.float32)
+        self._proj_t = proj_t.detach().to(dev, torch.float32).contiguous()
+        self._scale = float(render_scale)
+        self._skipped = torch.zeros(1, device=dev, dtype=torch.int32)
+        self.t = [0] * V
+        for v in range(V):
+            self._launch(v, None)
+
+    def camera(self, v: int):
+        """(viewmatrix [4, 4], projmatrix [4, 4], campos [3]) of view v: views
+        of the buffers s3x_pose_step rewrites."""
+        c = self.cameras[v]
+        return c[:16].view(4, 4), c[16:32].view(4, 4), c[32:35]
+
+    def _launch(self, v, grad):
+        t = max(self.t[v], 1)
+        hp = S3xPoseAdam(self.lr_translation, self.lr_rotation, self.betas[0], self.betas[1],
+                         self.eps, 1.0 - self.betas[0] ** t, math.sqrt(1.0 - self.betas[1] ** t),
+                         self._scale)
+        vm, pm, cp = self.camera(v)
+        dev = self.T_WC.device
+        with torch.cuda.device(dev):
+            _lib.call("s3x_pose_step", self.T_WC[v].data_ptr(), self.exp_avg[v].data_ptr(),
+                      self.exp_avg_sq[v].data_ptr(), None if grad is None else grad.data_ptr(),
+                      ctypes.byref(hp), self._proj_t.data_ptr(), vm.data_ptr(), pm.data_ptr(),
+                      cp.data_ptr(), _lib.stream(dev))
+
+    @torch.no_grad()
+    def step(self, v: int, grad: torch.Tensor) -> None:
+        """One step of view v on pose_gradient's output; nothing for a fixed
+        view."""
+        v = int(v)
+        if v in self.fixed:
+            return
+        if not torch.is_tensor(grad) or grad.dtype != torch.float64 or grad.numel() != 6:
+            raise ValueError("PoseControl.step: grad must be a float64 tensor of six entries")
+        _lib.require_cuda(grad)
+        self.t[v] += 1
+        self._launch(v, grad.contiguous())
+
+
+def _projection(K, H, W, near, far):
+    """The intrinsics-only part of render.camera_settings (scale-invariant),
+    on the host with its torch ops: (tanfovx, tanfovy, transposed projection
+    [4, 4], scale)."""
+    from splatt3r_amd.render import get_fov, get_projection_matrix, normalize_intrinsics
+    Kc = K.detach().to("cpu", torch.float32).reshape(3, 3)
+    nr, fr = torch.full((1,), float(near)), torch.full((1,), float(far))
+    scale = 1 / nr
+    fov_x, fov_y = get_fov(normalize_intrinsics(Kc[None], (H, W))).unbind(dim=-1)
+    proj_t = get_projection_matrix(nr * scale, fr * scale, fov_x, fov_y).transpose(1, 2)[0]
+    return (float((0.5 * fov_x).tan()[0]), float((0.5 * fov_y).tan()[0]), proj_t.contiguous(),
+            float(scale[0]))
+
+
+def _pose_cameras(poses, T_WC, K, H, W, near, far, bg, dev):
+    """_cameras with the pose part on the device in float64: starts the
+    PoseControl's run and returns (settings over its camera buffers, s)."""
+    from diff_gaussian_rasterization import GaussianRasterizationSettings
+    tx, ty, proj_t, s = _projection(K, H, W, near, far)
+    poses.begin(T_WC, proj_t, s, dev)
+    bgt = torch.tensor([0.0, 0.0, 0.0] if bg is None else list(bg), dtype=torch.float32,
+                       device=dev)
+    settings = []
+    for v in range(T_WC.shape[0]):
+        vm, pm, cp = poses.camera(v)
+        settings.append(GaussianRasterizationSettings(
+            image_height=H, image_width=W, tanfovx=tx, tanfovy=ty, bg=bgt, scale_modifier=1.0,
+            viewmatrix=vm, projmatrix=pm, sh_degree=0, campos=cp, prefiltered=False, debug=False))
+    return settings, s
+
+
+def _pose_loop(poses, settings, images, masks, order, iters, leaves, render, grad_kw, weights):
+    """The steps refine_poses and SharedGaussians.refine_pose share: render
+    view v from its device camera, photometric loss, backward, pose_gradient,
+    pose step.  leaves: the tensors whose .grad the backward fills (cleared
+    every step); render(settings) -> (image, radii); grad_kw() -> the keyword
+    arguments of pose_gradient after a backward."""
+    from splatt3r_amd.photometric import photometric_loss
+    history = torch.zeros(int(iters), device=images.device, dtype=torch.float32)
+    for it in range(int(iters)):
+        v = order[it % len(order)]
+        for t in leaves:
+            t.grad = None
+        frozen = v in poses.fixed
+        with torch.set_grad_enabled(not frozen):
+            img, radii = render(settings[v])
+            loss = photometric_loss(img[None], images[v:v + 1],
+                                    None if masks is None else masks[v:v + 1], **weights)
+        history[it] = loss.detach()
+        if frozen:
+            continue
+        loss.backward()
+        g = pose_gradient(settings[v].viewmatrix, radii=radii, skipped=poses._skipped,
+                          **grad_kw())
+        poses.step(v, g)
+    for t in leaves:
+        t.grad = None
+    return history
+
+
+def refine_poses(rows14, images, T_WC, K, iters, masks=None, poses=None, l1_weight=0.8,
+                 ssim_weight=0.2, mse_weight=0.0, near=0.1, far=1000.0, bg=None, order=None):
+    """Fit camera poses to images of a fixed map.  Arguments as refine_splats;
+    rows14 is not changed.  poses: a PoseControl (default PoseControl(): every
+    view moves; the map fixes the gauge).  One view per step, round-robin or
+    as `order` gives: activate once, then per step render from the view's
+    device camera -> photometric_loss -> backward -> pose_gradient (rotation
+    form, on that forward's radii) -> s3x_pose_step.  A view in poses.fixed is
+    rendered for its loss only.
+
+    Returns (T_WC, history): the refined poses, float64 [V, 4, 4] on the
+    device (also poses.T_WC), and the per-step losses [iters] as a device
+    tensor.  The loop reads nothing back from the device but the rasterizer's
+    instance count."""
+    from diff_gaussian_rasterization import GaussianRasterizer
+    _check_rows(rows14, "refine_poses")
+    dev = rows14.device
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise ValueError(f"refine_poses: images must be [V, 3, H, W], got {tuple(images.shape)}")
+    V, _, H, W = images.shape
+    if tuple(T_WC.shape) != (V, 4, 4):
+        raise ValueError(f"refine_poses: T_WC must be [{V}, 4, 4], got {tuple(T_WC.shape)}")
+    if masks is not None and tuple(masks.shape) != (V, H, W):
+        raise ValueError(f"refine_poses: masks must be [{V}, {H}, {W}]")
+    poses = PoseControl() if poses is None else poses
+    if not isinstance(poses, PoseControl):
+        raise TypeError("refine_poses: poses must be a PoseControl or None")
+    order = list(range(V)) if order is None else [int(v) for v in order]
+    if int(iters) > 0 and (not order or min(order) < 0 or max(order) >= V):
+        raise ValueError(f"refine_poses: order must index the {V} views")
+    images = images.to(dev, torch.float32).contiguous()
+    masks = None if masks is None else masks.to(dev, torch.float32).contiguous()
+    with torch.cuda.device(dev):
+        settings, s = _pose_cameras(poses, T_WC, K, H, W, near, far, bg, dev)
+        if rows14.shape[0] == 0 or int(iters) == 0:
+            return poses.T_WC, torch.zeros(int(iters), device=dev, dtype=torch.float32)
+        means3D, shs, opac, scales, rots = activate(rows14, s)
+        leaves = [t.requires_grad_(True) for t in (means3D, scales, rots)]
+        render = lambda st: GaussianRasterizer(st)(
+            means3D=means3D, means2D=torch.zeros_like(means3D), opacities=opac, shs=shs,
+            scales=scales, rotations=rots)
+        grad_kw = lambda: dict(means3D=means3D.detach(), d_means3D=means3D.grad,
+                               rotations=rots.detach(), d_rotations=rots.grad)
+        history = _pose_loop(poses, settings, images, masks, order, iters, leaves, render,
+                             grad_kw, dict(mse_weight=mse_weight, l1_weight=l1_weight,
+                                           ssim_weight=ssim_weight))
+    return poses.T_WC, history
+
+
+def localise(means3D, cov3D, colors, opacities, image, T_WC, K, iters, mask=None, poses=None,
+             l1_weight=0.8, ssim_weight=0.2, mse_weight=0.0, near=0.1, far=1000.0, bg=None):
+    """Fit one camera pose to one image of Gaussians given as the rasterizer
+    takes them from the map (SharedGaussians.refine_pose): means3D [n, 3] and
+    cov3D [n, 6] already times the scale-invariant factor 1 / near and its
+    square, colors [n, 3] (colors_precomp), opacities [n, 1]; the covariance
+    form of pose_gradient.  image [3, H, W], T_WC [4, 4].  None of the four
+    tensors is written.  Returns (T_WC float64 [4, 4] on the device,
+    history [iters])."""
+    from diff_gaussian_rasterization import GaussianRasterizer
+    dev = means3D.device
+    _lib.require_cuda(means3D, cov3D, colors, opacities)
+    image = image.reshape(1, 3, *image.shape[-2:]).to(dev, torch.float32).contiguous()
+    H, W = image.shape[-2:]
+    mask = None if mask is None else mask.reshape(1, H, W).to(dev, torch.float32).contiguous()
+    poses = PoseControl() if poses is None else poses
+    if not isinstance(poses, PoseControl):
+        raise TypeError("localise: poses must be a PoseControl or None")
+    with torch.cuda.device(dev):
+        settings, _ = _pose_cameras(poses, T_WC.reshape(1, 4, 4), K, H, W, near, far, bg, dev)
+        if means3D.shape[0] == 0 or int(iters) == 0:
+            return poses.T_WC[0], torch.zeros(int(iters), device=dev, dtype=torch.float32)
+        mu = means3D.detach().float().contiguous().clone().requires_grad_(True)
+        cov = cov3D.detach().float().contiguous().clone().requires_grad_(True)
+        render = lambda st: GaussianRasterizer(st)(
+            means3D=mu, means2D=torch.zeros_like(mu), opacities=opacities.detach(), shs=None,
+            colors_precomp=colors.detach(), cov3D_precomp=cov)
+        grad_kw = lambda: dict(means3D=mu.detach(), d_means3D=mu.grad, cov3D=cov.detach(),
+                               d_cov3D=cov.grad)
+        history = _pose_loop(poses, settings, image, mask, [0], iters, [mu, cov], render, grad_kw,
+                             dict(mse_weight=mse_weight, l1_weight=l1_weight,
+                                  ssim_weight=ssim_weight))
+    return poses.T_WC[0], history
