@@ -169,7 +169,11 @@ int s3n_attention(const s3n_attn_args* args, void* stream);
 
 /* Tuning hook (not on the product path), kernels for pre-rotated q/k:
  * 0 = transposed-score kernel with 2 key groups (default), 1 = the
- * P-through-LDS kernel, 2 = transposed-score with 1 key group, 3 = with 4;
+ * P-through-LDS kernel, 2 = transposed-score with 1 key group, 3 = with 4,
+ * 4 = transposed-score with 2 key groups and 32-query workgroups (2 query
+ * waves, 256 threads), 5 = the same with 128-query workgroups (8 query
+ * waves, 1024 threads); 0, 2 and 3 use 64-query workgroups.  Any other
+ * non-negative value selects the default kernel.
  * -1 / -2 = the transposed-score kernels' XCD-aware workgroup order off /
  * on (default on). */
 void s3n_attention_set_variant(int variant);
