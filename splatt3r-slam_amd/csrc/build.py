@@ -76,6 +76,7 @@ SOURCES = {
     "splat_opt.hip": STRICT,
     "splat_density.hip": STRICT,
     "pose_grad.hip": STRICT,
+    "map_compact.hip": STRICT,
 }
 
 

@@ -27,6 +27,7 @@ import torch
 
 from splatt3r_amd import _lib
 from splatt3r_amd import refine as _refine  # noqa: F401  (registers the s3d.h entry points)
+from splatt3r_amd import compact as _compact  # registers the s3v.h entry points
 
 
 class S3wMap(ctypes.Structure):
@@ -51,9 +52,33 @@ VIZ_BG = (0.118, 0.137, 0.149)
 class SharedGaussians:
     """frame.py:357-463 on the device: same fields, same append semantics."""
 
-    def __init__(self, manager=None, max_gaussians: int = 4 * 1024 * 1024, device="cuda"):
+    def __init__(self, manager=None, max_gaussians: int = 4 * 1024 * 1024, device="cuda",
+                 compact_voxel: Optional[float] = None):
+        """compact_voxel None: the reference's policy, a full map evicts its
+        oldest half.  A voxel size (world units; nobody has tuned it): an
+        append that could find the map full first merges the Gaussians that
+        share a voxel (`compact`), and the eviction is left for a map that
+        merging cannot shrink.  The object then keeps a host-side upper bound
+        of its count (every append adds its n_max; clear, load_ply, refine,
+        compact and n_gaussians make it exact), and an append compacts first
+        when bound + n_max > max_gaussians and the bound has grown by at least
+        max_gaussians // 8 since the last compaction's result (0 before the
+        first; clear and load_ply put that back to 0): no host read until the
+        map could be full, and no compaction per append of a map that stays
+        full.  The bound never exceeds max_gaussians, so after a compaction
+        that leaves more than 7/8 of max_gaussians the rule cannot be met
+        again: the map then evicts as the reference does, also after the
+        eviction has made room, until clear, load_ply or an explicit compact()
+        with a smaller result."""
         del manager  # single process per GPU: no multiprocessing manager/lock
         self.max_gaussians = int(max_gaussians)
+        if compact_voxel is not None:
+            compact_voxel, _ = _compact.check_grid(compact_voxel, (0.0, 0.0, 0.0),
+                                                   "SharedGaussians")
+        self.compact_voxel = compact_voxel
+        self.n_compactions = 0     # compact() calls that ran the merge
+        self._bound = 0            # host upper bound of the count (compact_voxel only)
+        self._compacted_to = 0     # the last compaction's result
         self.device = torch.device(device)
         cap = self.max_gaussians
         z = lambda *s, dt=torch.float32: torch.zeros(*s, device=self.device, dtype=dt)
@@ -71,7 +96,9 @@ class SharedGaussians:
     @property
     def n_gaussians(self) -> int:
         """Host read of the device count (synchronises the stream)."""
-        return int(self._n.item())
+        n = int(self._n.item())
+        self._bound = n
+        return n
 
     def _workspace(self, n):
         need = int(_lib.lib().s3w_map_append_workspace_bytes(n))
@@ -87,6 +114,11 @@ class SharedGaussians:
         n_max = records.shape[0]
         if n_max == 0:
             return
+        if self.compact_voxel is not None:
+            if (self._bound + n_max > self.max_gaussians
+                    and self._bound - self._compacted_to >= self.max_gaussians // 8):
+                self.compact(self.compact_voxel)
+            self._bound = min(self._bound + n_max, self.max_gaussians)
         records = records.float().contiguous()
         ws = self._workspace(n_max)
         _lib.call("s3w_map_append", ctypes.byref(self._c), records.data_ptr(), count.data_ptr(),
@@ -113,6 +145,49 @@ class SharedGaussians:
 
     def clear(self):
         self._n.zero_()
+        self._bound = self._compacted_to = 0
+
+    # ---- compaction (include/s3v.h, splatt3r_amd.compact) ----
+    def compact(self, voxel: float, origin=(0.0, 0.0, 0.0)) -> int:
+        """Merge the Gaussians whose centres share a voxel of side `voxel` on
+        the grid through `origin`, in place: s3v_merge into scratch buffers,
+        the five fields copied back, the device count set.  The map stays
+        oldest-first and kf_id non-decreasing where it was (a merged Gaussian
+        takes the place and the kf_id of its oldest member).  One host read,
+        of the new count, which is returned; an empty map returns 0.
+
+        The scratch (the five merged fields, s3v_merge's `first` and `group`,
+        which it requires and this method does not use, and its workspace,
+        about 110 bytes a row in all) is sized by the host bound of the count
+        where the map keeps one (compact_voxel given).  Without one the count
+        is known on the device only, so the scratch and the launch grids
+        cover max_gaussians rows whatever the map holds (0.47 GB at the
+        default 4 Mi; blocks past the count return at once), and an empty map
+        is found empty by the pass, not before it.  The scratch is freed on
+        return."""
+        voxel, origin = _compact.check_grid(voxel, origin, "SharedGaussians.compact")
+        # rows that may be live: the host bound where it is kept, else all
+        n_max = self.max_gaussians
+        if self.compact_voxel is not None:
+            n_max = min(self._bound, n_max)
+        if n_max == 0:
+            return 0
+        fields = (self.means, self.cov_triu, self.colors, self.opacities, self.kf_id)
+        dev = self.device
+        outs = tuple(torch.empty((n_max, *f.shape[1:]), device=dev, dtype=f.dtype)
+                     for f in fields)
+        first = torch.empty(n_max, device=dev, dtype=torch.int64)
+        group = torch.empty(n_max, device=dev, dtype=torch.int64)
+        tally = torch.zeros(2, device=dev, dtype=torch.int64)
+        _compact.launch_merge(fields, self._n, n_max, voxel, origin, outs, first, group, tally,
+                              _compact.workspace(n_max, dev))
+        m = int(tally[0].item())
+        for f, o in zip(fields, outs):
+            f[:m] = o[:m]
+        self._n.copy_(tally[:1])
+        self.n_compactions += 1
+        self._bound = self._compacted_to = m
+        return m
 
     # ---- 3DGS splat .ply (include/s3w.h, evaluate.write_splat_ply) ----
     def to_splats(self, n: Optional[int] = None, scale_min: float = 1e-7) -> torch.Tensor:
@@ -152,6 +227,7 @@ class SharedGaussians:
         dev_rows = torch.from_numpy(np.ascontiguousarray(rows14)).to(self.device)
         _lib.call("s3w_map_from_splats", ctypes.byref(self._c), dev_rows.data_ptr() if n else None,
                   n, int(kf_idx), _lib.stream(self.device))
+        self._bound, self._compacted_to = n, 0
         return n
 
     # ---- photometric refinement (include/s3o.h, splatt3r_amd.refine) ----
@@ -204,6 +280,7 @@ class SharedGaussians:
             keep = changed if f.dim() == 1 else changed[:, None]
             f[:m] = torch.where(keep, f[:m], o)
         self.kf_id[:m] = old[4]
+        self._bound = m
         return history
 
     def refine_pose(self, image, T_WC, K, iters, near: float = 0.1, **kw):

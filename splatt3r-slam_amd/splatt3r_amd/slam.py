@@ -189,7 +189,8 @@ class Frontend:
                  depth_max_percentile=0.98, max_scale=1.0, min_confidence=1.5,
                  readback=True, enc_batch=1, main_priority=None, late_prefetch=False,
                  viz=False, max_gaussians=4 * 1024 * 1024, backend=None, render_writer=None,
-                 decode_ahead=False, enc_ahead=None, render_async=False, deferred_render=True):
+                 decode_ahead=False, enc_ahead=None, render_async=False, deferred_render=True,
+                 map_compact_voxel=None):
         self.model = model
         # dataio.RenderWriter: the per-frame gs_init_* / gs_track_* PNG export
         # (main.py:436-446, 490-506), written off the tracking thread
@@ -201,7 +202,10 @@ class Frontend:
         self.viz = viz
         # the world map the viz process renders (frame.py:357-463); appended
         # to with opacity > 0.3 (main.py:426-433, 480-487)
-        self.gmap = SharedGaussians(max_gaussians=max_gaussians, device=device) if viz else None
+        # map_compact_voxel: the map merges co-located Gaussians before it would
+        # evict (SharedGaussians compact_voxel); None: the reference's eviction
+        self.gmap = SharedGaussians(max_gaussians=max_gaussians, device=device,
+                                    compact_voxel=map_compact_voxel) if viz else None
         self.map_opacity_threshold = 0.3
         self.device = device
         self.K = K
