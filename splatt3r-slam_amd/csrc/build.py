@@ -77,6 +77,7 @@ SOURCES = {
     "splat_density.hip": STRICT,
     "pose_grad.hip": STRICT,
     "map_compact.hip": STRICT,
+    "map_reanchor.hip": STRICT,
 }
 
 

@@ -73,6 +73,10 @@ SIGNATURES: dict[str, tuple] = {
     # s3o.h (hp: POINTER(refine.S3oAdam), passed with ctypes.byref)
     "s3o_activate": (I32, [P, I64, F32, P, P, P, P, P, P]),
     "s3o_adam_step": (I32, [P, P, P, I64, P, P, P, P, P, P, P, P, P]),
+    # s3a.h (map: POINTER(gaussian_map.S3wMap), passed with ctypes.byref)
+    "s3a_reanchor_workspace_bytes": (SZ, [ctypes.c_int32]),
+    "s3a_map_reanchor": (I32, [P, P, P, ctypes.c_int32, P, P, P, SZ, P]),
+    "s3a_set_path": (None, [I32]),
 }
 
 _lock = threading.Lock()

@@ -53,8 +53,13 @@ class SharedGaussians:
     """frame.py:357-463 on the device: same fields, same append semantics."""
 
     def __init__(self, manager=None, max_gaussians: int = 4 * 1024 * 1024, device="cuda",
-                 compact_voxel: Optional[float] = None):
-        """compact_voxel None: the reference's policy, a full map evicts its
+                 compact_voxel: Optional[float] = None, max_keyframes: int = 512):
+        """max_keyframes: rows the anchor table starts with (`anchors`, the
+        pose each keyframe's Gaussians are expressed under, all unset; it
+        grows when a keyframe index exceeds it).  Nothing reads the table
+        until `reanchor` is called.
+
+        compact_voxel None: the reference's policy, a full map evicts its
         oldest half.  A voxel size (world units; nobody has tuned it): an
         append that could find the map full first merges the Gaussians that
         share a voxel (`compact`), and the eviction is left for a map that
@@ -89,6 +94,11 @@ class SharedGaussians:
         self.kf_id = z(cap, dt=torch.int32)
         self._n = z(1, dt=torch.int64)
         self._ws = torch.empty(0, dtype=torch.uint8, device=self.device)
+        # re-anchoring (include/s3a.h): the pose table, the per-keyframe
+        # deltas' workspace, the {moved, held} counters
+        self.anchors = z(max(1, int(max_keyframes)), 8)
+        self._ws_anchor = torch.empty(0, dtype=torch.float64, device=self.device)
+        self._tally = z(2, dt=torch.int64)
         self._c = S3wMap(self.means.data_ptr(), self.cov_triu.data_ptr(), self.colors.data_ptr(),
                          self.opacities.data_ptr(), self.kf_id.data_ptr(), self._n.data_ptr(),
                          cap)
@@ -146,6 +156,66 @@ class SharedGaussians:
     def clear(self):
         self._n.zero_()
         self._bound = self._compacted_to = 0
+        self.anchors.zero_()     # every keyframe unset
+
+    # ---- re-anchoring (include/s3a.h) ----
+    def _anchor_rows(self, n_kf: int):
+        """The anchor table with at least n_kf rows (reallocate and copy)."""
+        have = self.anchors.shape[0]
+        if n_kf > have:
+            grown = torch.zeros(max(n_kf, 2 * have), 8, device=self.device)
+            grown[:have] = self.anchors
+            self.anchors = grown
+        return self.anchors
+
+    def set_anchor(self, kf_idx: int, T_WC=None):
+        """Record that the Gaussians labelled kf_idx are expressed under the
+        pose T_WC (a lietorch.Sim3 of one pose or 8 floats [t, q xyzw, s]):
+        one 8-float device copy.  None unsets the row."""
+        kf_idx = int(kf_idx)
+        if kf_idx < 0:
+            raise ValueError(f"SharedGaussians.set_anchor: kf_idx {kf_idx} < 0")
+        if T_WC is None:
+            if kf_idx < self.anchors.shape[0]:
+                self.anchors[kf_idx].zero_()
+            return
+        row = (T_WC.data if hasattr(T_WC, "data") and not torch.is_tensor(T_WC) else T_WC)
+        row = torch.as_tensor(row, dtype=torch.float32).reshape(8)
+        self._anchor_rows(kf_idx + 1)[kf_idx].copy_(row, non_blocking=True)
+
+    def reanchor(self, poses, count: bool = False):
+        """Move every Gaussian with its keyframe (s3a_map_reanchor): `poses`,
+        [n_kf, 8] or a lietorch.Sim3 of n_kf poses, are the keyframes' current
+        poses; a Gaussian labelled k < n_kf whose anchor row differs from
+        poses[k] gets mu' = t_n + M (mu - t_o), Sigma' = M Sigma M^T with
+        M = (s_n / s_o) R_n R_o^T, and the anchor rows take the poses.  An
+        unset anchor adopts its pose and moves nothing; an invalid pose
+        (non-finite, s <= 0, zero quaternion) holds its keyframe.  Colours,
+        opacities, kf_id and the count are not written.  Two launches on the
+        current stream.  count=True returns (rows moved, keyframes held), one
+        host read; otherwise None and no host read."""
+        rows = poses.data if hasattr(poses, "data") and not torch.is_tensor(poses) else poses
+        rows = rows.reshape(-1, 8)
+        _lib.require_cuda(rows)
+        n_kf = rows.shape[0]
+        if n_kf == 0:
+            return (0, 0) if count else None
+        rows = rows.to(self.device, torch.float32).contiguous()
+        anchors = self._anchor_rows(n_kf)
+        need = int(_lib.lib().s3a_reanchor_workspace_bytes(n_kf))
+        if self._ws_anchor.numel() * 8 < need:
+            self._ws_anchor = torch.empty((need + 7) // 8, dtype=torch.float64,
+                                          device=self.device)
+        tally = self._tally if count else None
+        with torch.cuda.device(self.device):
+            _lib.call("s3a_map_reanchor", ctypes.byref(self._c), anchors.data_ptr(),
+                      rows.data_ptr(), n_kf, tally.data_ptr() if count else None,
+                      tally[1:].data_ptr() if count else None, self._ws_anchor.data_ptr(),
+                      self._ws_anchor.numel() * 8, _lib.stream(self.device))
+        if count:
+            moved, held = tally.tolist()
+            return moved, held
+        return None
 
     # ---- compaction (include/s3v.h, splatt3r_amd.compact) ----
     def compact(self, voxel: float, origin=(0.0, 0.0, 0.0)) -> int:

@@ -190,7 +190,7 @@ class Frontend:
                  readback=True, enc_batch=1, main_priority=None, late_prefetch=False,
                  viz=False, max_gaussians=4 * 1024 * 1024, backend=None, render_writer=None,
                  decode_ahead=False, enc_ahead=None, render_async=False, deferred_render=True,
-                 map_compact_voxel=None):
+                 map_compact_voxel=None, map_follow_poses=False):
         self.model = model
         # dataio.RenderWriter: the per-frame gs_init_* / gs_track_* PNG export
         # (main.py:436-446, 490-506), written off the tracking thread
@@ -207,6 +207,21 @@ class Frontend:
         self.gmap = SharedGaussians(max_gaussians=max_gaussians, device=device,
                                     compact_voxel=map_compact_voxel) if viz else None
         self.map_opacity_threshold = 0.3
+        # map_follow_poses: the map moves with its keyframes.  Every Gaussian
+        # labelled k is kept expressed under keyframe k's installed pose: a new
+        # keyframe records its pose as the label's anchor, and whenever the
+        # backend's pose writes are installed the map is re-anchored to
+        # keyframes.get_poses() (SharedGaussians.reanchor, include/s3a.h)
+        # before the next frame is tracked.  The option's one deviation from
+        # the reference: a tracked, non-keyframe append is labelled
+        # len(keyframes) - 1, the keyframe it was tracked against (its pose is
+        # relative to that keyframe); the reference's len(keyframes) names a
+        # keyframe that does not exist yet.  Off (the default): no label, no
+        # launch and no map byte differs from the reference's.
+        self.map_follow_poses = bool(map_follow_poses) and self.gmap is not None
+        # poses may have been written outside apply_pending (a backend without
+        # a worker thread solves inside _kf_added / relocalization)
+        self._map_stale = False
         self.device = device
         self.K = K
         self.late_prefetch = late_prefetch
@@ -416,6 +431,24 @@ class Frontend:
                 e, self._rworker.error = self._rworker.error, None
                 raise e
 
+    def sync_map(self):
+        """Re-anchor the map to the keyframes' current poses
+        (map_follow_poses; SharedGaussians.reanchor) on the stream the map's
+        appends were issued on: the kernel skips every keyframe whose pose
+        has not changed.  Covers poses installed outside a step
+        (Backend.wait()).  Returns (Gaussians moved, keyframes held: those
+        whose pose is not a valid Sim3), one host read; None when the map
+        does not follow the poses."""
+        if not self.map_follow_poses:
+            return None
+        self._map_stale = False
+        if len(self.keyframes) == 0:
+            return (0, 0)
+        st = self.main_stream if self.main_stream is not None else \
+            torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(st):
+            return self.gmap.reanchor(self.keyframes.get_poses(), count=True)
+
     def save_map(self, path):
         """Write the Gaussian map as a 3DGS splat .ply (evaluate.
         save_gaussian_splats) once every queued render has been issued.
@@ -423,6 +456,7 @@ class Frontend:
         keeps no map (viz off) or the map is empty."""
         from splatt3r_amd.evaluate import save_gaussian_splats
         self.drain()
+        self.sync_map()
         path = pathlib.Path(path)
         # on the stream the map's appends were issued on
         st = self.main_stream if self.main_stream is not None else \
@@ -444,6 +478,7 @@ class Frontend:
         self.drain()
         if self.gmap is None or len(self.keyframes) == 0:
             return None
+        self.sync_map()
         # on the stream the map's appends were issued on
         st = self.main_stream if self.main_stream is not None else \
             torch.cuda.current_stream(self.device)
@@ -815,9 +850,23 @@ class Frontend:
             self._stats["gaussians_world"] = int(self._gw_count.item())
         return self._stats
 
+    def _append_label(self, frame, add_new_kf):
+        """kf_id of a tracked frame's append: the reference's len(keyframes)
+        (main.py:480-487), which is the new keyframe's index when the frame
+        becomes one.  map_follow_poses: a new keyframe records its pose as
+        that label's anchor; any other frame takes the label of the keyframe
+        it was tracked against."""
+        if not self.map_follow_poses:
+            return len(self.keyframes)
+        if add_new_kf:
+            self.gmap.set_anchor(len(self.keyframes), frame.T_WC)
+            return len(self.keyframes)
+        return len(self.keyframes) - 1
+
     def _kf_added(self, frame):
         """states.queue_global_optimization (main.py:409, 525-526)."""
         if self.backend is not None:
+            self._map_stale = True
             idx = len(self.keyframes) - 1
             self.backend.on_keyframe(idx, frame)
             self.backend.queue_global_optimization(idx)
@@ -859,7 +908,12 @@ class Frontend:
             mark("delivered")
         # keyframe poses the backend worker has finished optimising
         # (SharedKeyframes' in-place writes, frame.py:269-330)
-        self.keyframes.apply_pending()
+        installed = self.keyframes.apply_pending()
+        if self.map_follow_poses and (installed or self._map_stale) and len(self.keyframes):
+            # before tracking: what is appended next is placed under the
+            # installed poses.  Stream-ordered, no host read.
+            self._map_stale = False
+            self.gmap.reanchor(self.keyframes.get_poses())
         T_WC = (lietorch.Sim3.Identity(1, device=self.device) if self.last_T_WC is None
                 else self.last_T_WC)
         frame = self._take_prefetched(i, T_WC)
@@ -904,6 +958,8 @@ class Frontend:
             self._stats["keyframes"] += 1
             self._kf_added(frame)
             self.mode = Mode.TRACKING
+            if self.map_follow_poses:
+                self.gmap.set_anchor(len(self.keyframes) - 1, frame.T_WC)
             if self._to_world(frame, len(self.keyframes) - 1) is not None and self.viz:
                 self.last_append_T_WC, self.last_append_idx = frame.T_WC, i
             self._render(frame, frame, None, prefix="gs_init")
@@ -945,7 +1001,8 @@ class Frontend:
                     self.min_translation, self.min_frame_gap):
                 if spec is not None:
                     self._keep_world_records(frame, spec[0])
-                elif self._to_world(frame, len(self.keyframes)) is not None and self.viz:
+                elif self._to_world(frame, self._append_label(frame, add_new_kf)) is not None \
+                        and self.viz:
                     self.last_append_T_WC, self.last_append_idx = frame.T_WC, i
             if not try_reloc:
                 if spec is not None and isinstance(spec[1], _RenderTicket):
@@ -968,7 +1025,19 @@ class Frontend:
             self._stats["reloc"] += 1
             if self.backend is not None:
                 self.backend.wait()
-                if self.backend.relocalization(frame):
+                ok = self.backend.relocalization(frame)
+                if self.map_follow_poses:
+                    # accepted: later appends tracked against the new keyframe
+                    # carry its label, placed under the pose it has now (the
+                    # solve may already have written it).  Rejected: the
+                    # keyframe was popped, its index names nothing.
+                    self._map_stale = True
+                    if ok:
+                        self.gmap.set_anchor(len(self.keyframes) - 1,
+                                             self.keyframes[len(self.keyframes) - 1].T_WC)
+                    else:
+                        self.gmap.set_anchor(len(self.keyframes), None)
+                if ok:
                     self._stats["keyframes"] += 1
                     self.new_kf_frames.append(i)
                     self._last_kf_i, self._kf_fracs = i, []
