@@ -78,6 +78,7 @@ SOURCES = {
     "pose_grad.hip": STRICT,
     "map_compact.hip": STRICT,
     "map_reanchor.hip": STRICT,
+    "tsdf_mesh.hip": STRICT,
 }
 
 

@@ -77,6 +77,16 @@ SIGNATURES: dict[str, tuple] = {
     "s3a_reanchor_workspace_bytes": (SZ, [ctypes.c_int32]),
     "s3a_map_reanchor": (I32, [P, P, P, ctypes.c_int32, P, P, P, SZ, P]),
     "s3a_set_path": (None, [I32]),
+    # s3f.h
+    "s3f_integrate_workspace_bytes": (SZ, [ctypes.c_int32]),
+    "s3f_integrate": (I32, [P, P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, F32, F32, F32,
+                            F32, F32, F32, P, P, P, P, P, ctypes.c_int32, ctypes.c_int32,
+                            ctypes.c_int32, P, SZ, P]),
+    "s3f_mesh_workspace_bytes": (SZ, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "s3f_mesh_count": (I32, [P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, F32, P, P, SZ,
+                             P]),
+    "s3f_mesh_emit": (I32, [P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, F32, F32, F32,
+                            F32, I64, I64, P, P, P, I64, I64, P, SZ, P]),
 }
 
 _lock = threading.Lock()

@@ -245,6 +245,129 @@ def save_gaussian_splats(savedir, filename, gmap):
     return gmap.save_ply(savedir / filename)
 
 
+# ------------------------------------------------------ triangle mesh .ply ----
+def write_mesh_ply(path, verts, colors, faces):
+    """Write a triangle mesh as a binary little-endian .ply: `vertex` with
+    x y z float and red green blue uchar (colors in [0, 1], clamped, times 255
+    rounded to nearest), `face` with vertex_indices as list uchar int.  Host
+    arrays [nv, 3], [nv, 3], [nt, 3]; a mesh without triangles (or vertices)
+    is a valid file."""
+    verts = np.asarray(verts, np.float32).reshape(-1, 3)
+    colors = np.asarray(colors, np.float32).reshape(-1, 3)
+    faces = np.asarray(faces).reshape(-1, 3)
+    if len(colors) != len(verts):
+        raise ValueError(f"write_mesh_ply: {len(verts)} vertices but {len(colors)} colours")
+    if len(faces) and (faces.min() < 0 or faces.max() >= len(verts)):
+        raise ValueError("write_mesh_ply: a face index is out of range")
+    vrec = np.empty(len(verts), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"),
+                                       ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    vrec["x"], vrec["y"], vrec["z"] = verts.T
+    c8 = np.rint(np.clip(np.nan_to_num(colors), 0.0, 1.0) * 255.0).astype(np.uint8)
+    vrec["red"], vrec["green"], vrec["blue"] = c8.T
+    frec = np.empty(len(faces), dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    frec["n"] = 3
+    frec["v"] = faces
+    header = ("ply\nformat binary_little_endian 1.0\n"
+              f"element vertex {len(verts)}\n"
+              "property float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+              f"element face {len(faces)}\n"
+              "property list uchar int vertex_indices\nend_header\n")
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(vrec.tobytes())
+        f.write(frec.tobytes())
+
+
+def read_mesh_ply(path):
+    """Read a binary little-endian triangle-mesh .ply: (verts [nv, 3] float32,
+    colors [nv, 3] uint8 or None, faces [nt, 3] int32).  Vertex properties are
+    found by name (any order, extra ones skipped); the face element must
+    follow the vertex element with one list property (`vertex_indices` or
+    `vertex_index`) whose every entry has 3 indices.  Raises ValueError
+    otherwise."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    if not raw.startswith(b"ply"):
+        raise ValueError(f"{path}: not a PLY file")
+    end = raw.find(b"end_header\n")
+    if end < 0:
+        raise ValueError(f"{path}: PLY header has no end_header line")
+    offset = end + len(b"end_header\n")
+    fmt, elements = None, []          # [name, count, [(prop, dtype) | ("list", name, ct, it)]]
+    for line in raw[:end].decode("ascii", errors="replace").split("\n")[1:]:
+        tok = line.split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append([tok[1], int(tok[2]), []])
+        elif tok[0] == "property":
+            if not elements:
+                raise ValueError(f"{path}: property before any element")
+            types = tok[2:4] if tok[1] == "list" else tok[1:2]
+            if any(t not in _PLY_TYPES for t in types):
+                raise ValueError(f"{path}: unknown property type in {line!r}")
+            if tok[1] == "list":
+                elements[-1][2].append(("list", tok[4], "<" + _PLY_TYPES[tok[2]],
+                                        "<" + _PLY_TYPES[tok[3]]))
+            else:
+                elements[-1][2].append((tok[2], "<" + _PLY_TYPES[tok[1]]))
+    if fmt != "binary_little_endian":
+        raise ValueError(f"{path}: only binary_little_endian PLY is read, file is {fmt}")
+    names = [e[0] for e in elements]
+    if names[:1] != ["vertex"]:
+        raise ValueError(f"{path}: the first element must be vertex")
+    _, nv, vprops = elements[0]
+    if any(p[0] == "list" for p in vprops):
+        raise ValueError(f"{path}: list property in the vertex element")
+    vdt = np.dtype(vprops)
+    for p in ("x", "y", "z"):
+        if p not in vdt.names:
+            raise ValueError(f"{path}: missing property {p!r}")
+    if len(raw) - offset < nv * vdt.itemsize:
+        raise ValueError(f"{path}: truncated vertex body")
+    vrec = np.frombuffer(raw, dtype=vdt, count=nv, offset=offset)
+    offset += nv * vdt.itemsize
+    verts = np.stack([vrec[p].astype(np.float32) for p in ("x", "y", "z")], 1).reshape(-1, 3)
+    colors = None
+    if all(p in vdt.names for p in ("red", "green", "blue")):
+        colors = np.stack([vrec[p].astype(np.uint8) for p in ("red", "green", "blue")],
+                          1).reshape(-1, 3)
+    faces = np.zeros((0, 3), np.int32)
+    if len(elements) > 1:
+        name, nt, fprops = elements[1]
+        if name != "face" or len(fprops) != 1 or fprops[0][0] != "list" \
+                or fprops[0][1] not in ("vertex_indices", "vertex_index"):
+            raise ValueError(f"{path}: expected a face element with one vertex_indices list")
+        fdt = np.dtype([("n", fprops[0][2]), ("v", fprops[0][3], (3,))])
+        if len(raw) - offset < nt * fdt.itemsize:
+            raise ValueError(f"{path}: truncated face body")
+        frec = np.frombuffer(raw, dtype=fdt, count=nt, offset=offset)
+        if nt and (frec["n"] != 3).any():
+            raise ValueError(f"{path}: only triangles are read")
+        faces = np.ascontiguousarray(frec["v"]).astype(np.int32).reshape(-1, 3)
+    return verts, colors, faces
+
+
+def save_mesh(savedir, filename, gmap, T_WC, K, H, W, voxel, **kw):
+    """Extract the Gaussian map's surface (SharedGaussians.extract_mesh, which
+    takes **kw) and write it as a triangle-mesh .ply into savedir, created
+    like save_reconstruction does.  Returns (vertices, triangles) written, or
+    None when there is no map, it is empty or there is no view."""
+    if gmap is None:
+        return None
+    mesh = gmap.extract_mesh(T_WC, K, H, W, voxel, **kw)
+    if mesh is None:
+        return None
+    verts, colors, faces = (t.cpu().numpy() for t in mesh)
+    savedir = pathlib.Path(savedir)
+    savedir.mkdir(exist_ok=True, parents=True)
+    write_mesh_ply(savedir / filename, verts, colors, faces)
+    return len(verts), len(faces)
+
+
 def save_keyframes(savedir, timestamps, keyframes):
     from PIL import Image
     savedir = pathlib.Path(savedir)

@@ -376,6 +376,85 @@ class SharedGaussians:
         return localise(sc_means, sc_cov, self.colors[:n], self.opacities[:n, None], image, T_WC, K,
                         iters, near=near, **kw)
 
+    # ---- surface extraction (include/s3f.h, splatt3r_amd.mesh) ----
+    @torch.no_grad()
+    def render_depths(self, T_WC, K, H, W, alpha_min: float = 0.5, near: float = 0.1,
+                      far: float = 1000.0, n: Optional[int] = None):
+        """What extract_mesh fuses: the map rendered from the V camera-to-world
+        poses T_WC [V, 4, 4] as refine_pose and render_map feed the rasterizer
+        (s3w_map_scale, cov3D_precomp, colors_precomp, the cameras of
+        refine._cameras, return_depth=True).  Returns (depth [V, H, W] in each
+        view's camera units: depth / alpha where alpha >= alpha_min, else 0,
+        with the scale-invariant factor undone; color [V, 3, H, W] clamped to
+        [0, 1]; K_r [3, 3], the rasterizer's own pinhole,
+        mesh.rasterizer_intrinsics), or None for an empty map."""
+        from diff_gaussian_rasterization import GaussianRasterizer
+        from splatt3r_amd.mesh import rasterizer_intrinsics
+        from splatt3r_amd.refine import _cameras
+        if n is None:
+            n = self.n_gaussians
+        if n == 0:
+            return None
+        dev = self.device
+        T_WC = torch.as_tensor(T_WC).reshape(-1, 4, 4)
+        with torch.cuda.device(dev):
+            settings, s = _cameras(T_WC, K, H, W, near, far, None, dev)
+            sc_means = torch.empty(n, 3, device=dev)
+            sc_cov = torch.empty(n, 6, device=dev)
+            _lib.call("s3w_map_scale", self.means.data_ptr(), self.cov_triu.data_ptr(),
+                      self._n.data_ptr(), n, s, s * s, sc_means.data_ptr(), sc_cov.data_ptr(),
+                      _lib.stream(dev))
+            depths, colors = [], []
+            for st in settings:
+                out = GaussianRasterizer(st)(
+                    means3D=sc_means, means2D=torch.zeros_like(sc_means), shs=None,
+                    colors_precomp=self.colors[:n], opacities=self.opacities[:n, None],
+                    cov3D_precomp=sc_cov, return_depth=True)
+                depth, alpha = out[2], out[3]
+                depths.append(torch.where(alpha >= alpha_min, depth / alpha,
+                                          torch.zeros_like(depth)) / s)
+                colors.append(out[0].clamp(0, 1))
+            return (torch.stack(depths).contiguous(), torch.stack(colors).contiguous(),
+                    rasterizer_intrinsics(settings[0]))
+
+    @torch.no_grad()
+    def extract_mesh(self, T_WC, K, H, W, voxel, bounds=None, alpha_min: float = 0.5,
+                     near: float = 0.1, far: float = 1000.0, w_min: float = 1.0,
+                     view_batch: int = 16, **volume_kw):
+        """A triangle mesh of the map's surface: depth and colour rendered
+        from the map at the views T_WC [V, 4, 4] (camera-to-world (s R | t),
+        intrinsics K, H x W; render_depths), fused into a mesh.TSDFVolume of
+        spacing `voxel` (view_batch views per launch) and extracted by
+        marching tetrahedra.  The fusion projects with the rasterizer's own
+        pinhole, not K (mesh.rasterizer_intrinsics).
+
+        bounds None: the axis-aligned box of the map's means (one host read),
+        padded by the truncation distance.  A box that needs more voxels than
+        the ABI's limit or `max_voxels` (a volume_kw, like trunc and w_max)
+        raises ValueError naming the count and the smallest voxel that fits.
+        The map is read only: its five fields keep their bits.  Returns
+        (verts [nv, 3], colors [nv, 3] in [0, 1], faces [nt, 3] int32) on the
+        device, or None for an empty map or no view."""
+        from splatt3r_amd.mesh import TSDFVolume
+        n = self.n_gaussians
+        T_WC = torch.as_tensor(T_WC).reshape(-1, 4, 4)
+        if n == 0 or T_WC.shape[0] == 0:
+            return None
+        voxel = float(voxel)
+        trunc = float(volume_kw.get("trunc") or 4.0 * voxel)
+        if bounds is None:
+            lo, hi = torch.aminmax(self.means[:n], dim=0)
+            lo, hi = torch.stack([lo, hi]).tolist()
+            bounds = ([v - trunc for v in lo], [v + trunc for v in hi])
+        with torch.cuda.device(self.device):
+            vol = TSDFVolume(bounds=bounds, voxel=voxel, device=self.device, **volume_kw)
+            step = max(1, int(view_batch))
+            for a in range(0, T_WC.shape[0], step):
+                depth, color, K_r = self.render_depths(T_WC[a:a + step], K, H, W, alpha_min, near,
+                                                       far, n=n)
+                vol.integrate(depth, T_WC[a:a + step], K_r, color=color)
+            return vol.extract(w_min=w_min)
+
 
 def splats_from_cov(means, cov_triu, colors, opacities, scale_min: float = 1e-7) -> torch.Tensor:
     """[n, 17] splat rows (include/s3w.h s3w_map_to_splats) of n Gaussians

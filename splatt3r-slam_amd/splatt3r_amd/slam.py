@@ -492,6 +492,35 @@ class Frontend:
                  else self.K.detach().to("cpu", torch.float32).reshape(-1, 3, 3)[0])
             return self.gmap.refine(images, poses, K, iters, **kw)
 
+    def save_mesh(self, path, voxel, **kw):
+        """Write the Gaussian map's surface as a triangle-mesh .ply
+        (evaluate.save_mesh: depth rendered from the map at every keyframe's
+        pose, TSDF fusion at spacing `voxel`, marching tetrahedra) once every
+        queued render has been issued: pose the 4 x 4 (s R | t) of kf.T_WC,
+        intrinsics K or the default estimate, image size the keyframes', as
+        refine_map takes them.  **kw goes to SharedGaussians.extract_mesh.
+        Never called by the frame loop.  Returns (vertices, triangles)
+        written, or None when the session keeps no map (viz off), the map is
+        empty or there is no keyframe."""
+        from splatt3r_amd.evaluate import keyframe_target, save_mesh
+        from splatt3r_amd.splatt3r_utils import _estimate_default_intrinsics
+        self.drain()
+        if self.gmap is None or len(self.keyframes) == 0:
+            return None
+        self.sync_map()
+        path = pathlib.Path(path)
+        # on the stream the map's appends were issued on
+        st = self.main_stream if self.main_stream is not None else \
+            torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(st):
+            dev = self.gmap.device
+            kfs = [self.keyframes[i] for i in range(len(self.keyframes))]
+            poses = torch.cat([_sim3_to_4x4(kf.T_WC).to(dev).reshape(1, 4, 4) for kf in kfs])
+            h, w = keyframe_target(kfs[0]).shape[-2:]
+            K = (_estimate_default_intrinsics(h, w, "cpu") if self.K is None
+                 else self.K.detach().to("cpu", torch.float32).reshape(-1, 3, 3)[0])
+            return save_mesh(path.parent, path.name, self.gmap, poses, K, h, w, voxel, **kw)
+
     def close(self):
         """End the session: wait for queued renders, stop the render worker
         thread and release the decode-ahead slot this session left on the
