@@ -70,6 +70,7 @@ SOURCES = {
     "gn_backend.hip": STRICT,
     "retrieval.hip": STRICT,
     "ingest.hip": STRICT,
+    "undistort.hip": STRICT,
     "photometric.hip": STRICT,
     "loss_mask.hip": STRICT,
     "splat_io.hip": STRICT,

@@ -3,6 +3,9 @@ the reference's FPS window (main.py:363-535):
 
   TUMDataset      splatt3r_slam/dataloader.py:18-60 (+ TUM rgb.txt parsing,
                   :63-78): dataset[i] -> (timestamp, HxWx3 float32 in [0, 1])
+  EurocDataset    dataloader.py:92-116: mav0/cam0 (data.csv, sensor.yaml,
+                  data/*.png), greyscale, always undistorted
+  load_dataset    dataloader.py:320-327: the reader by the path's segments
   FrameLoader     dataset[i] -> create_frame's host work (resize_img: PIL
                   LANCZOS 640x480 -> 512x384 + centre crop + ImgNorm,
                   splatt3r_utils.py:658-693, frame.py:122-133) -> pinned
@@ -14,13 +17,17 @@ the reference's FPS window (main.py:363-535):
                   :490-506 `gs_track_*`): D2H of the rendered [1,1,3,H,W]
                   image into a pinned ring, then uint8 conversion and the
                   PNG write on writer threads
+  write_synthetic_euroc  a EuRoC-layout sequence of 752x480 greyscale frames
+                  with MH_01's cam0 calibration
   write_synthetic_tum  a TUM-layout sequence (rgb/*.png + rgb.txt) of 640x480
                   frames for the benchmark when fr1_desk itself is absent
 
 The reference does all of this synchronously in the tracking loop (its
 dataset read, its resize and its cv2.imwrite sit between the GPU calls);
 here the host work runs on threads that overlap the GPU, with the same
-bytes in and out: the frames the tracker sees are resize_img's output, and
+bytes in and out: the frames the tracker sees are resize_img's output (of
+the undistorted frame when the dataset is calibrated: intrinsics.py, cv2.remap
+restated; on the device with ingest="device"), and
 each PNG holds `uint8(clamp(render, 0, 1) * 255)` (truncation, as the
 reference's `.astype("uint8")`), in RGB order (cv2 writes the BGR array it
 was given, i.e. RGB on disk; PIL writes RGB).  cv2 is not installed here:
@@ -32,6 +39,7 @@ import concurrent.futures as cf
 import os
 import pathlib
 import queue
+import re
 import threading
 from typing import Optional
 
@@ -40,12 +48,61 @@ import torch
 
 
 # ------------------------------------------------------------------ input --
-class TUMDataset:
+# dataloader.py:76-89: fx fy cx cy [k1 k2 p1 p2 k3] of the three TUM cameras
+TUM_CALIB = {
+    1: (517.3, 516.5, 318.6, 255.3, 0.2624, -0.9531, -0.0054, 0.0026, 1.1633),
+    2: (520.9, 521.0, 325.1, 249.7, 0.2312, -0.7849, -0.0033, -0.0001, 0.9172),
+    3: (535.4, 539.2, 320.1, 247.6),
+}
+
+
+class MonocularDataset:
+    """dataloader.py:20-64: dataset[i] -> (timestamp, img float32 [H,W,3] in
+    [0, 1], RGB).  With `use_calibration` the frame is undistorted first
+    (camera_intrinsics.remap on the uint8 image, on the host here; the
+    FrameLoader's device mode does it on the GPU)."""
+
+    def __init__(self, dtype=np.float32):
+        from splatt3r_amd.config import config
+        self.dtype = dtype
+        self.rgb_files: list = []
+        self.timestamps = np.zeros(0, dtype=np.float64)
+        self.img_size = 512
+        self.camera_intrinsics = None
+        self.use_calibration = bool(config["use_calib"])
+
+    def __len__(self):
+        return len(self.rgb_files)
+
+    def read_img(self, idx) -> np.ndarray:
+        from PIL import Image
+        with Image.open(self.rgb_files[idx]) as im:
+            return np.asarray(im.convert("RGB"))
+
+    def get_image(self, idx) -> np.ndarray:
+        img = self.read_img(idx)
+        if self.use_calibration and self.camera_intrinsics is not None:
+            img = self.camera_intrinsics.remap(img)
+        if img.ndim == 2:                                   # greyscale: GRAY2BGR
+            img = np.repeat(img[..., None], 3, axis=2)
+        return img.astype(self.dtype) / 255.0
+
+    def __getitem__(self, idx):
+        return self.timestamps[idx], self.get_image(idx)
+
+    def has_calib(self) -> bool:
+        return self.camera_intrinsics is not None
+
+
+class TUMDataset(MonocularDataset):
     """TUM RGB-D layout (rgb.txt: "timestamp rgb/<file>.png", '#' comments),
-    dataloader.py:18-78: __getitem__ -> (timestamp, img float32 [H,W,3] in
-    [0, 1], RGB).  cv2.imread + BGR2RGB in the reference; PIL reads RGB."""
+    dataloader.py:67-89.  cv2.imread + BGR2RGB in the reference; PIL reads
+    RGB.  A path that names its camera (`freiburg1` .. `freiburg3`) gets that
+    camera's calibration (used when config use_calib is on); any other path
+    has none."""
 
     def __init__(self, root, subsample: int = 1):
+        super().__init__()
         self.root = pathlib.Path(root)
         rows = []
         with open(self.root / "rgb.txt") as f:
@@ -57,20 +114,103 @@ class TUMDataset:
         rows = rows[::subsample]
         self.timestamps = np.array([t for t, _ in rows], dtype=np.float64)
         self.rgb_files = [p for _, p in rows]
-        self.img_size = 512
-        self.dtype = np.float32
+        m = re.search(r"freiburg(\d+)", str(root))
+        if m is not None and int(m.group(1)) in TUM_CALIB:
+            from splatt3r_amd.intrinsics import Intrinsics
+            self.camera_intrinsics = Intrinsics.from_calib(self.img_size, 640, 480,
+                                                           TUM_CALIB[int(m.group(1))])
+        if self.camera_intrinsics is None:
+            self.use_calibration = False
 
-    def __len__(self):
-        return len(self.rgb_files)
+
+class EurocDataset(MonocularDataset):
+    """EuRoC MAV layout, dataloader.py:92-116: mav0/cam0/data.csv
+    ("timestamp [ns],filename", '#' comments), mav0/cam0/sensor.yaml
+    (resolution, intrinsics, distortion_coefficients) and
+    mav0/cam0/data/*.png.  Always undistorted ("the distortion is too much to
+    handle for MASt3R"), whether or not use_calib is on.  read_img returns
+    the greyscale frame uint8 [H,W]; timestamps are int64 nanoseconds."""
+
+    def __init__(self, root, subsample: int = 1):
+        super().__init__()
+        import yaml
+        from splatt3r_amd.intrinsics import Intrinsics
+        self.use_calibration = True
+        self.root = pathlib.Path(root)
+        cam0 = self.root / "mav0" / "cam0"
+        rows = []
+        with open(cam0 / "data.csv") as f:
+            for line in f:
+                if line.startswith("#") or not line.strip():
+                    continue
+                t, name = (v.strip() for v in line.split(",")[:2])
+                rows.append((int(t), cam0 / "data" / name))
+        rows = rows[::subsample]
+        self.timestamps = np.array([t for t, _ in rows], dtype=np.int64)
+        self.rgb_files = [p for _, p in rows]
+        with open(cam0 / "sensor.yaml") as f:
+            self.cam0 = yaml.safe_load(f)
+        W, H = self.cam0["resolution"]
+        calib = [*self.cam0["intrinsics"], *self.cam0["distortion_coefficients"]]
+        self.camera_intrinsics = Intrinsics.from_calib(self.img_size, W, H, calib,
+                                                       always_undistort=True)
 
     def read_img(self, idx) -> np.ndarray:
         from PIL import Image
         with Image.open(self.rgb_files[idx]) as im:
-            return np.asarray(im.convert("RGB"))
+            return np.asarray(im.convert("L"))
 
-    def __getitem__(self, idx):
-        img = self.read_img(idx)
-        return self.timestamps[idx], img.astype(self.dtype) / 255.0
+
+def load_dataset(path):
+    """dataloader.py:320-327: the reader named by a segment of the path
+    (`tum` or `euroc`)."""
+    parts = str(path).split("/")
+    if "tum" in parts:
+        return TUMDataset(path)
+    if "euroc" in parts:
+        return EurocDataset(path)
+    raise ValueError(f"load_dataset: no reader for {str(path)!r}: the path needs a segment "
+                     "'tum' or 'euroc' (the reference's other kinds -- eth3d, 7-scenes, "
+                     "realsense, webcam, video and plain image folders -- are not served)")
+
+
+# MH_01 cam0 (mav0/cam0/sensor.yaml of the EuRoC MAV dataset)
+EUROC_RESOLUTION = (752, 480)
+EUROC_INTRINSICS = (458.654, 457.296, 367.215, 248.375)
+EUROC_DISTORTION = (-0.28340811, 0.07395907, 0.00019359, 1.76187114e-05)
+
+
+def write_synthetic_euroc(root, n: int, seed: int = 0, step_px: float = 2.5) -> pathlib.Path:
+    """A EuRoC-layout sequence of n 752x480 greyscale PNG frames (the texture
+    of write_synthetic_tum) with MH_01's cam0 sensor.yaml, for tests and for
+    users without the dataset."""
+    from PIL import Image
+    from splatt3r_amd.synthetic import smooth_texture
+    root = pathlib.Path(root)
+    cam0 = root / "mav0" / "cam0"
+    (cam0 / "data").mkdir(parents=True, exist_ok=True)
+    W, H = EUROC_RESOLUTION
+    pad = int(np.ceil(step_px * n)) + 8
+    tex = smooth_texture(H + pad, W + pad, seed).mean(0)    # [H', W'] in [0, 1]
+    lines = ["#timestamp [ns],filename"]
+    for i in range(n):
+        oy = int(round(0.5 * step_px * i)) + 4
+        ox = int(round(step_px * i)) + 4
+        t = 1403636579763555584 + i * 50000000              # 20 Hz
+        Image.fromarray(np.round(tex[oy:oy + H, ox:ox + W] * 255).astype(np.uint8)).save(
+            cam0 / "data" / f"{t}.png", compress_level=1)
+        lines.append(f"{t},{t}.png")
+    (cam0 / "data.csv").write_text("\n".join(lines) + "\n")
+    (cam0 / "sensor.yaml").write_text(
+        "# synthetic EuRoC-layout sequence, MH_01 cam0 calibration\n"
+        "sensor_type: camera\n"
+        "rate_hz: 20\n"
+        f"resolution: [{W}, {H}]\n"
+        "camera_model: pinhole\n"
+        f"intrinsics: [{', '.join(repr(v) for v in EUROC_INTRINSICS)}]\n"
+        "distortion_model: radial-tangential\n"
+        f"distortion_coefficients: [{', '.join(repr(v) for v in EUROC_DISTORTION)}]\n")
+    return root
 
 
 def write_synthetic_tum(root, n: int, H: int = 480, W: int = 640, seed: int = 0,
@@ -133,7 +273,14 @@ class FrameLoader:
         "device" (the raw uint8 frame is uploaded and ingest.resize_img_device
         resizes, crops and normalises it on the loader's stream; the same
         `img`, and `uimg` stays on the device).  None: the environment
-        variable S3_INGEST, default "host"."""
+        variable S3_INGEST, default "host".
+
+        A dataset with `use_calibration` set has its frames undistorted with
+        `dataset.camera_intrinsics` before the resize, in both modes and with
+        identical `img` and `uimg`: "device" runs the HIP remap (s3u_remap)
+        in front of the ingest launch on the loader's stream; "host" runs the
+        numpy restatement intrinsics.remap_u8 on the worker, which is slow
+        (tens of milliseconds per frame) and correct."""
         self.ds = dataset
         self.device = torch.device(device)
         self.img_size = img_size
@@ -153,6 +300,8 @@ class FrameLoader:
         self._futs: dict = {}
         self._depth = depth
         self._lock = threading.Lock()
+        self._undistort = (getattr(dataset, "camera_intrinsics", None)
+                           if getattr(dataset, "use_calibration", False) else None)
         self._fill()
 
     def _fill(self):
@@ -164,7 +313,7 @@ class FrameLoader:
 
     def _load_device(self, i) -> LoadedFrame:
         from splatt3r_amd.ingest import resize_img_device
-        raw = self.ds.read_img(i)                          # uint8 [H, W, 3]
+        raw = self.ds.read_img(i)                          # uint8 [H, W, 3] (greyscale: [H, W])
         slot = self._ring.get()
         try:
             buf, busy = slot
@@ -177,7 +326,8 @@ class FrameLoader:
                 dev = buf.to(self.device, non_blocking=True)
                 slot[1] = torch.cuda.Event()
                 slot[1].record(self.stream)
-                r = resize_img_device(dev, self.img_size, stream=self.stream)
+                r = resize_img_device(dev, self.img_size, stream=self.stream,
+                                      undistort=self._undistort)
                 ev = torch.cuda.Event()
                 ev.record(self.stream)
         finally:

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from splatt3r_amd import _lib
+from splatt3r_amd import intrinsics as _intrinsics  # noqa: F401  (registers the s3u_* signatures)
 
 LANCZOS = "lanczos"
 BICUBIC = "bicubic"
@@ -222,16 +223,24 @@ def _cuda_device(device) -> torch.device:
 
 
 def resize_img_device(img_u8, size, square_ok=False, return_transformation=False,
-                      device="cuda", stream=None):
+                      device="cuda", stream=None, undistort=None):
     """resize_img on the device.  img_u8: uint8 [H,W,3] or [B,H,W,3], numpy
     array or tensor, on the host or the device (a device tensor decides the
     device).  Returns resize_img's dict: img float32 [B,3,h,w] and
     unnormalized_img uint8 [B,h,w,3] ([h,w,3] for a 3-D input) on the device,
     true_shape np.int32 [[h, w]] * B; with return_transformation also its
     tuple.  The upload and the launch go to `stream` (default: the current
-    stream); nothing waits for them."""
-    src = _check_input(img_u8)
-    batched = img_u8.ndim == 4
+    stream); nothing waits for them.
+
+    undistort: an intrinsics.Intrinsics (or UndistortMap).  The frame is then
+    first undistorted on the device (s3u_remap, include/s3u.h: cv2.remap with
+    the camera's maps) and the result ingested, both on `stream`; the input
+    may then also be greyscale ([H,W], [H,W,1] or [B,H,W,1])."""
+    if undistort is not None:
+        src, batched = undistort.remap_device(img_u8, device, stream)
+    else:
+        src = _check_input(img_u8)
+        batched = img_u8.ndim == 4
     dev = src.device if src.is_cuda else _cuda_device(device)
     B, in_h, in_w, _ = src.shape
     (W, H), filt, box, tr = ingest_geometry(in_h, in_w, size, square_ok)

@@ -36,6 +36,7 @@ import threading
 import time
 import types
 
+import numpy as np
 import torch
 
 import lietorch
@@ -190,7 +191,7 @@ class Frontend:
                  readback=True, enc_batch=1, main_priority=None, late_prefetch=False,
                  viz=False, max_gaussians=4 * 1024 * 1024, backend=None, render_writer=None,
                  decode_ahead=False, enc_ahead=None, render_async=False, deferred_render=True,
-                 map_compact_voxel=None, map_follow_poses=False):
+                 map_compact_voxel=None, map_follow_poses=False, intrinsics=None):
         self.model = model
         # dataio.RenderWriter: the per-frame gs_init_* / gs_track_* PNG export
         # (main.py:436-446, 490-506), written off the tracking thread
@@ -227,6 +228,16 @@ class Frontend:
         self.late_prefetch = late_prefetch
         self.keyframes = Keyframes()
         if config["use_calib"]:
+            # intrinsics: a dataset (its camera_intrinsics) or an
+            # intrinsics.Intrinsics; its K_frame is the camera of the
+            # network's input (main.py:314-318).  An explicit K wins.
+            if K is None and intrinsics is not None:
+                intr = getattr(intrinsics, "camera_intrinsics", intrinsics)
+                if intr is None:
+                    raise ValueError("use_calib: the dataset has no calibration "
+                                     "(main.py:310-312)")
+                K = self.K = torch.from_numpy(np.asarray(intr.K_frame)).to(
+                    device, dtype=torch.float32)
             if K is None:
                 raise ValueError("use_calib needs the camera intrinsics K (main.py:310-318)")
             self.keyframes.set_intrinsics(K)   # main.py:314-318
