@@ -28,6 +28,7 @@
 
 #include "common.hpp"
 #include "s3w.h"
+#include "wave_scan.hpp"
 
 namespace {
 
@@ -160,15 +161,6 @@ __device__ __forceinline__ float fval(uint32_t k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
-
 __global__ void __launch_bounds__(kSelThreads)
 k_g2w_select(int n, Grid g, const float* __restrict__ means, const float* __restrict__ scales,
              const float* __restrict__ conf, float depth_min, float q, float max_scale,
@@ -179,7 +171,6 @@ k_g2w_select(int n, Grid g, const float* __restrict__ means, const float* __rest
   __shared__ uint32_t wpart[kSelThreads / 64];
   __shared__ uint32_t sel[2][2];   // [rank][prefix, remaining rank]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  constexpr int NW = kSelThreads / 64;
   // depth keys (+ the count n0 of z > depth_min); consecutive threads take
   // consecutive Gaussians, 4 loads in flight per thread
   uint32_t cnt = 0;
@@ -190,12 +181,8 @@ k_g2w_select(int n, Grid g, const float* __restrict__ means, const float* __rest
     keys[i] = ok ? fkey(z) : 0xFFFFFFFFu;
     cnt += ok ? 1u : 0u;
   }
-  cnt = wave_incl_scan(cnt, lane);
-  if (lane == 63) wpart[wave] = cnt;
-  __syncthreads();
   uint32_t n0 = 0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) n0 += wpart[w];
+  s3::block_excl_add<kSelThreads>(cnt, wpart, &n0);
   const bool use_q = n0 > 0 && q < 1.0f;
   float zq = 0.0f;
   if (use_q) {
@@ -224,7 +211,7 @@ k_g2w_select(int n, Grid g, const float* __restrict__ means, const float* __rest
         uint32_t h[4], sum = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) { h[j] = hist[wave][4 * lane + j]; sum += h[j]; }
-        const uint32_t incl = wave_incl_scan(sum, lane);
+        const uint32_t incl = s3::wave_incl_add(sum, lane);
         const uint64_t hit = __ballot(rem < incl);
         const int L = __ffsll((unsigned long long)hit) - 1;
         if (lane == L) {
@@ -257,15 +244,8 @@ k_g2w_select(int n, Grid g, const float* __restrict__ means, const float* __rest
   const int c0 = min(n, tid * chunk), c1 = min(n, c0 + chunk);
   uint32_t mine = 0;
   for (int i = c0; i < c1; ++i) mine += kept[i];
-  const uint32_t incl = wave_incl_scan(mine, lane);
-  if (lane == 63) wpart[wave] = incl;   // (the n0 reads of wpart are behind a barrier)
-  __syncthreads();
-  uint32_t base = incl - mine, total = 0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) {
-    if (w < wave) base += wpart[w];
-    total += wpart[w];
-  }
+  uint32_t total = 0;
+  uint32_t base = s3::block_excl_add<kSelThreads>(mine, wpart, &total);
   if (tid == 0) *count = (int64_t)total;
   for (int i = c0; i < c1; ++i) {
     const bool k = kept[i];
@@ -286,24 +266,6 @@ k_g2w_emit(int64_t n, Grid g, s3w_view v, const float* __restrict__ T44,
 
 // ---- multi-pass path (n > kSelMax) ---------------------------------------
 
-// block-wide exclusive scan of one value per thread (kThreads threads)
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t* s_w, uint32_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  constexpr int NW = kThreads / 64;
-  const uint32_t incl = wave_incl_scan(x, lane);
-  if (lane == 63) s_w[wave] = incl;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) {
-    if (w < wave) base += s_w[w];
-    tot += s_w[w];
-  }
-  __syncthreads();
-  if (total) *total = tot;
-  return base + incl - x;
-}
-
 __global__ void __launch_bounds__(kThreads)
 k_prep(int64_t n, Grid g, const float* __restrict__ means, float depth_min,
        uint32_t* __restrict__ keys, uint32_t* __restrict__ sel) {
@@ -316,7 +278,7 @@ k_prep(int64_t n, Grid g, const float* __restrict__ means, float depth_min,
     keys[i] = ok ? fkey(z) : 0xFFFFFFFFu;
   }
   uint32_t tot = 0;
-  block_excl_scan(ok ? 1u : 0u, s_w, &tot);
+  s3::block_excl_add<kThreads>(ok ? 1u : 0u, s_w, &tot);
   if (threadIdx.x == 0 && tot) atomicAdd(&sel[4], tot);   // n0 (integer: order-free)
 }
 
@@ -357,7 +319,7 @@ k_sel_pick(uint32_t* __restrict__ hist, uint32_t* __restrict__ sel, int shift, f
   uint32_t h[4], sum = 0;
 #pragma unroll
   for (int j = 0; j < 4; ++j) { h[j] = hist[wave * 256 + 4 * lane + j]; sum += h[j]; }
-  const uint32_t incl = wave_incl_scan(sum, lane);
+  const uint32_t incl = s3::wave_incl_add(sum, lane);
   const uint64_t hit = __ballot(rem < incl);
   const int L = hit ? __ffsll((unsigned long long)hit) - 1 : -1;
   if (lane == L) {
@@ -399,7 +361,7 @@ k_flags(int64_t n, Grid g, const float* __restrict__ means, const float* __restr
     flags[i] = f;
   }
   uint32_t tot = 0;
-  block_excl_scan(f, s_w, &tot);
+  s3::block_excl_add<kThreads>(f, s_w, &tot);
   if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 
@@ -408,24 +370,7 @@ k_flags(int64_t n, Grid g, const float* __restrict__ means, const float* __restr
 __global__ void __launch_bounds__(1024)
 k_scan_blocks(uint32_t* __restrict__ bsum, int64_t nblk, int64_t* __restrict__ count) {
   __shared__ uint32_t s_w[16];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t carry = 0;
-  for (int64_t c0 = 0; c0 < nblk; c0 += 1024) {
-    const int64_t c = c0 + threadIdx.x;
-    const uint32_t v = c < nblk ? bsum[c] : 0u;
-    const uint32_t incl = wave_incl_scan(v, lane);
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-      if (w < wave) base += s_w[w];
-      tot += s_w[w];
-    }
-    if (c < nblk) bsum[c] = carry + base + incl - v;
-    carry += tot;
-    __syncthreads();
-  }
+  const uint32_t carry = s3::block_excl_add_array<1024>(bsum, nblk, s_w);
   if (threadIdx.x == 0) {
     bsum[nblk] = carry;
     if (count) *count = (int64_t)carry;
@@ -439,7 +384,7 @@ k_emit(int64_t n, Grid g, s3w_view v, const float* __restrict__ T44,
   __shared__ uint32_t s_w[kThreads / 64];
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   const uint32_t f = i < n ? flags[i] : 0u;
-  const uint32_t off = bsum[blockIdx.x] + block_excl_scan(f, s_w, nullptr);
+  const uint32_t off = bsum[blockIdx.x] + s3::block_excl_add<kThreads>(f, s_w, nullptr);
   if (f) emit_record(v, g, T44, g.pix(i), out + (int64_t)off * 13);
 }
 
@@ -540,7 +485,7 @@ k_map_flags(int64_t n_max, const float* __restrict__ rec, const int64_t* __restr
     flags[i] = f;
   }
   uint32_t tot = 0;
-  block_excl_scan(f, s_w, &tot);
+  s3::block_excl_add<kThreads>(f, s_w, &tot);
   if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 
@@ -577,7 +522,7 @@ k_map_emit(int64_t n_max, s3w_map m, const float* __restrict__ rec,
   __shared__ uint32_t s_w[kThreads / 64];
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   const uint32_t f = i < n_max ? flags[i] : 0u;
-  const int64_t off = (int64_t)bsum[blockIdx.x] + block_excl_scan(f, s_w, nullptr);
+  const int64_t off = (int64_t)bsum[blockIdx.x] + s3::block_excl_add<kThreads>(f, s_w, nullptr);
   const int64_t n0 = *n0p;
   const int64_t space = m.cap - n0;
   if (i == n_max - 1) {

@@ -5,8 +5,8 @@
 //   k_mc_pack        keys packed to that range, order kept, dropped rows
 //                    behind every group; the index column of the sort
 //   sort             stable LSD radix sort of (key, index), up to eight 8-bit
-//                    passes: k_mc_hist -> k_mc_row_scan -> k_mc_scatter, the
-//                    scheme of raster.hip's passes with 64-bit keys; all
+//                    passes: k_mc_hist -> k_mc_row_scan -> k_mc_scatter
+//                    (the shared pass of radix_pass.hpp with 64-bit keys); all
 //                    eight are launched, those past the packed width return
 //   k_mc_heads       group heads in sorted order; the head flag of each input
 //                    row; group = -1 of the dropped rows
@@ -24,6 +24,7 @@
 // floating-point atomic (the two counters are integers).
 #include <algorithm>
 #include "common.hpp"
+#include "radix_pass.hpp"
 #include "s3v.h"
 
 namespace {
@@ -215,232 +216,46 @@ k_mc_pack(const int64_t* __restrict__ n_dev, int64_t n_max, const uint32_t* __re
 }
 
 // ---------------------------------------------------------------- sort ----
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ uint64_t lanemask_lt(int lane) { return (1ull << lane) - 1ull; }
-
-// lanes of `active` holding the same 8-bit digit as this lane
-__device__ __forceinline__ uint64_t match_peers(uint32_t d, bool active) {
-  uint64_t peers = __ballot(active);
-#pragma unroll
-  for (int b = 0; b < kBits; ++b) {
-    const bool set = (d >> b) & 1u;
-    const uint64_t m = __ballot(active && set);
-    peers &= set ? m : ~m;
+// The bodies of a pass are radix_pass.hpp's with 64-bit keys and a fixed
+// 8-bit digit; a pass past the packed width returns at once.
+struct Digit {
+  int shift;
+  static constexpr int bits = kBits, max_bits = kBits;
+  __device__ __forceinline__ uint32_t operator()(uint64_t key) const {
+    return (uint32_t)(key >> shift) & (uint32_t)(kBins - 1);
   }
-  return peers;
-}
-
-__device__ __forceinline__ uint32_t wave_incl_add(uint32_t v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
-__device__ __forceinline__ uint32_t wave_incl_max(uint32_t v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(v, o, 64);
-    if (lane >= o) v = max(v, t);
-  }
-  return v;
-}
-
-// exclusive sum of one value per thread across a workgroup of NT threads
-template <int NT>
-__device__ __forceinline__ uint32_t block_excl_add(uint32_t v, uint32_t* s_w,
-                                                   uint32_t* total = nullptr) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const uint32_t inc = wave_incl_add(v, lane);
-  if (lane == 63) s_w[w] = inc;
-  __syncthreads();
-  uint32_t base = 0, all = 0;
-#pragma unroll
-  for (int k = 0; k < NT / 64; ++k) {
-    base += k < w ? s_w[k] : 0u;
-    all += s_w[k];
-  }
-  __syncthreads();
-  if (total) *total = all;
-  return base + inc - v;
-}
-
-// exclusive running maximum (identity 0) likewise
-template <int NT>
-__device__ __forceinline__ uint32_t block_excl_max(uint32_t v, uint32_t* s_w,
-                                                   uint32_t* total = nullptr) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const uint32_t inc = wave_incl_max(v, lane);
-  if (lane == 63) s_w[w] = inc;
-  __syncthreads();
-  uint32_t base = 0, all = 0;
-#pragma unroll
-  for (int k = 0; k < NT / 64; ++k) {
-    base = max(base, k < w ? s_w[k] : 0u);
-    all = max(all, s_w[k]);
-  }
-  __syncthreads();
-  if (total) *total = all;
-  const uint32_t prev = __shfl_up(inc, 1, 64);
-  return max(base, lane ? prev : 0u);
-}
-
-__device__ __forceinline__ uint32_t digit(uint64_t key, int shift) {
-  return (uint32_t)(key >> shift) & (uint32_t)(kBins - 1);
-}
+};
 
 // digit counts of every kSeg-item block -> hist[digit][block]
 __global__ void __launch_bounds__(kT)
 k_mc_hist(const int64_t* __restrict__ n_dev, int64_t n_max, const uint64_t* __restrict__ keys,
           int shift, int64_t nseg, uint32_t* __restrict__ hist,
           const uint32_t* __restrict__ meta, const unsigned long long* __restrict__ dropped) {
-  __shared__ uint32_t cnt[kBins];
   if (shift >= plan_of(meta, dropped).passes * kBits) return;
-  const int64_t n = live_n(n_dev, n_max);
-  cnt[threadIdx.x] = 0u;
-  __syncthreads();
-  const int64_t s = blockIdx.x;
-  const int64_t i0 = s * kSeg;
-  if (i0 < n) {
-    uint64_t key[kPer];
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) {
-      const int64_t i = i0 + j * kT + threadIdx.x;
-      key[j] = i < n ? keys[i] : 0ull;
-    }
-#pragma unroll
-    for (int j = 0; j < kPer; ++j)
-      if (i0 + j * kT + threadIdx.x < n) atomicAdd(&cnt[digit(key[j], shift)], 1u);
-  }
-  __syncthreads();
-  hist[(size_t)threadIdx.x * nseg + s] = cnt[threadIdx.x];
+  s3::radix_hist<kT, kPer, uint64_t, uint64_t>(live_n(n_dev, n_max), keys, Digit{shift}, nseg,
+                                               hist);
 }
 
-// Per digit row: exclusive scan over `cols` blocks in place, row total to
-// tot[row].  Wave w owns a contiguous quarter of the columns.
+// per digit row: exclusive scan over `cols` blocks in place, row total to tot[row]
 __global__ void __launch_bounds__(kT)
 k_mc_row_scan(uint32_t* __restrict__ hist, int64_t cols, uint32_t* __restrict__ tot, int shift,
               const uint32_t* __restrict__ meta, const unsigned long long* __restrict__ dropped) {
-  constexpr int NW = kT / 64;
-  __shared__ uint32_t s_q[NW];
   if (shift >= plan_of(meta, dropped).passes * kBits) return;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t* h = hist + (size_t)blockIdx.x * cols;
-  const int64_t per = (cols + NW - 1) / NW;
-  const int64_t q0 = min(cols, (int64_t)w * per), q1 = min(cols, q0 + per);
-  uint32_t sum = 0;
-  for (int64_t c = q0 + lane; c < q1; c += 64) sum += h[c];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-  if (lane == 0) s_q[w] = sum;
-  __syncthreads();
-  uint32_t carry = 0, all = 0;
-#pragma unroll
-  for (int k = 0; k < NW; ++k) {
-    carry += k < w ? s_q[k] : 0u;
-    all += s_q[k];
-  }
-  for (int64_t c0 = q0; c0 < q1; c0 += 64) {
-    const int64_t c = c0 + lane;
-    const uint32_t v = c < q1 ? h[c] : 0u;
-    const uint32_t inc = wave_incl_add(v, lane);
-    if (c < q1) h[c] = carry + inc - v;
-    carry += __shfl(inc, 63, 64);
-  }
-  if (threadIdx.x == 0) tot[blockIdx.x] = all;
+  s3::radix_row_scan<kT, 1>(hist, cols, tot);
 }
 
-// One block of kSeg items: wave w owns items [w * 512, (w + 1) * 512) of it,
-// in 8 windows of 64.
 __global__ void __launch_bounds__(kT)
 k_mc_scatter(const int64_t* __restrict__ n_dev, int64_t n_max, const uint64_t* __restrict__ kin,
              const uint32_t* __restrict__ vin, uint64_t* __restrict__ kout,
              uint32_t* __restrict__ vout, int shift, int64_t nseg,
              const uint32_t* __restrict__ hist, const uint32_t* __restrict__ tot,
              const uint32_t* __restrict__ meta, const unsigned long long* __restrict__ dropped) {
-  constexpr int NW = kT / 64;
   if (shift >= plan_of(meta, dropped).passes * kBits) return;
-  __shared__ uint32_t cnt[NW][kBins];  // per-wave counts -> local slots
-  __shared__ uint32_t gdelta[kBins];   // global slot - local slot, per digit
-  __shared__ uint32_t s_w[NW];
-  __shared__ uint64_t sk[kSeg];
-  __shared__ uint32_t sv[kSeg];
   const int64_t n = live_n(n_dev, n_max);
-  const int64_t s = blockIdx.x;
-  const int64_t seg0 = s * kSeg;
-  if (seg0 >= n) return;
-#pragma unroll
-  for (int k = 0; k < NW; ++k) cnt[k][threadIdx.x] = 0u;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t base_w = seg0 + (int64_t)w * 64 * kPer;
-  uint64_t key[kPer];
-  uint32_t val[kPer];
-#pragma unroll
-  for (int j = 0; j < kPer; ++j) {
-    const int64_t i = base_w + j * 64 + lane;
-    key[j] = i < n ? kin[i] : 0ull;
-    val[j] = i < n ? vin[i] : 0u;
-  }
-#pragma unroll
-  for (int j = 0; j < kPer; ++j)
-    if (base_w + j * 64 + lane < n) atomicAdd(&cnt[w][digit(key[j], shift)], 1u);
-  __syncthreads();
-  // local slots (digit-major within the block) and the global offset of each
-  // digit's run; thread d owns digit d
-  {
-    const int d = threadIdx.x;
-    uint32_t tb = 0;
-#pragma unroll
-    for (int k = 0; k < NW; ++k) tb += cnt[k][d];
-    const uint32_t lbase = block_excl_add<kT>(tb, s_w);
-    const uint32_t gbase = block_excl_add<kT>(tot[d], s_w);
-    gdelta[d] = gbase + hist[(size_t)d * nseg + s] - lbase;
-    uint32_t b = lbase;
-#pragma unroll
-    for (int k = 0; k < NW; ++k) {
-      const uint32_t c = cnt[k][d];
-      cnt[k][d] = b;
-      b += c;
-    }
-  }
-  __syncthreads();
-  // local slot = the wave's running slot + rank among equal digits in the
-  // window (stable by construction); stage key and value there
-#pragma unroll
-  for (int j = 0; j < kPer; ++j) {
-    const bool ok = base_w + j * 64 + lane < n;
-    const uint32_t d = digit(key[j], shift);
-    const uint64_t peers = match_peers(d, ok);
-    if (ok) {
-      const uint32_t b = cnt[w][d];
-      const uint32_t lp = b + (uint32_t)__popcll(peers & lanemask_lt(lane));
-      if ((peers >> lane) == 1ull) cnt[w][d] = b + (uint32_t)__popcll(peers);
-      sk[lp] = key[j];
-      sv[lp] = val[j];
-    }
-    wave_lds_sync();
-  }
-  __syncthreads();
-  // runs of equal digits go to consecutive global slots
-  const int m = (int)min<int64_t>(kSeg, n - seg0);
-#pragma unroll
-  for (int j = 0; j < kPer; ++j) {
-    const int lp = j * kT + threadIdx.x;
-    if (lp < m) {
-      const uint64_t k = sk[lp];
-      const uint32_t gp = (uint32_t)lp + gdelta[digit(k, shift)];
-      kout[gp] = k;
-      vout[gp] = sv[lp];
-    }
-  }
+  if ((int64_t)blockIdx.x * kSeg >= n) return;
+  __builtin_assume(vin != nullptr && kout != nullptr);   // the body's two null options are raster's
+  s3::radix_scatter<kT, kPer, uint64_t, uint64_t>(n, kin, vin, kout, vout, Digit{shift}, nseg,
+                                                  hist, tot);
 }
 
 // ------------------------------------------------------ heads and scans ----
@@ -484,8 +299,8 @@ k_mc_scan_sums(const int64_t* __restrict__ n_dev, int64_t n_max, const uint32_t*
       sm += isf[i0 + q];
     }
   uint32_t tmx, tsm;
-  block_excl_max<kT>(mx, s_w, &tmx);
-  block_excl_add<kT>(sm, s_w, &tsm);
+  s3::block_excl_max<kT>(mx, s_w, &tmx);
+  s3::block_excl_add<kT>(sm, s_w, &tsm);
   if (threadIdx.x == 0) {
     bsum[blockIdx.x] = tmx;
     bsum[nblk + blockIdx.x] = tsm;
@@ -502,8 +317,8 @@ k_mc_scan_top(int64_t nblk, uint32_t* __restrict__ bsum, int64_t* __restrict__ m
     const uint32_t mx = b < nblk ? bsum[b] : 0u;
     const uint32_t sm = b < nblk ? bsum[nblk + b] : 0u;
     uint32_t tmx, tsm;
-    const uint32_t emx = block_excl_max<kTop>(mx, s_w, &tmx);
-    const uint32_t esm = block_excl_add<kTop>(sm, s_w, &tsm);
+    const uint32_t emx = s3::block_excl_max<kTop>(mx, s_w, &tmx);
+    const uint32_t esm = s3::block_excl_add<kTop>(sm, s_w, &tsm);
     if (b < nblk) {
       bsum[b] = max(cmx, emx);
       bsum[nblk + b] = csm + esm;
@@ -529,8 +344,8 @@ k_mc_scan_apply(const int64_t* __restrict__ n_dev, int64_t n_max, uint32_t* __re
     mx = max(mx, a[q]);
     sm += f[q];
   }
-  uint32_t rmx = max(bsum[blockIdx.x], block_excl_max<kT>(mx, s_w));
-  uint32_t rsm = bsum[nblk + blockIdx.x] + block_excl_add<kT>(sm, s_w);
+  uint32_t rmx = max(bsum[blockIdx.x], s3::block_excl_max<kT>(mx, s_w));
+  uint32_t rsm = bsum[nblk + blockIdx.x] + s3::block_excl_add<kT>(sm, s_w);
 #pragma unroll
   for (int q = 0; q < kPer; ++q)
     if (i0 + q < n) {

@@ -10,6 +10,7 @@
 #include "common.hpp"
 #include "device_util.hpp"
 #include "s3m.h"
+#include "wave_scan.hpp"
 
 #include <map>
 #include <mutex>
@@ -617,22 +618,13 @@ constexpr int kScanBlock = 1024;
 // contiguous run of tiles per thread), counts reset to zero
 __global__ void __launch_bounds__(kScanBlock)
 k_refine_scan(int* __restrict__ cnt, int* __restrict__ off, int total) {
-  __shared__ int wsum[kScanBlock / 64];
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  __shared__ uint32_t wsum[kScanBlock / 64];
+  const int t = threadIdx.x;
   const int per = (total + kScanBlock - 1) / kScanBlock;
   const int lo = t * per, hi = min(lo + per, total);
   int s = 0;
   for (int k = lo; k < hi; ++k) s += cnt[k];
-  int x = s;                                  // inclusive scan over the wave
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wsum[wv] = x;
-  __syncthreads();
-  int run = x - s;
-  for (int k = 0; k < wv; ++k) run += wsum[k];
+  int run = (int)s3::block_excl_add<kScanBlock>((uint32_t)s, wsum);
   for (int k = lo; k < hi; ++k) {
     const int c = cnt[k];
     off[k] = run;

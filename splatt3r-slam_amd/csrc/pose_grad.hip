@@ -17,6 +17,7 @@
 // No floating-point atomic anywhere: the result is a pure function of the
 // inputs and n.  The skipped counter is an integer atomic.
 // k_pose_step      one thread (s3x::pose_step, s3x::pose_camera).
+#include "arg_check.hpp"
 #include "common.hpp"
 #include "pose_grad_math.hpp"
 #include "s3x.h"
@@ -140,10 +141,6 @@ __global__ void k_pose_step(double* __restrict__ T_WC, double* __restrict__ exp_
   for (int k = 0; k < 3; ++k) campos[k] = fc[k];
 }
 
-inline bool aligned(const void* p, uintptr_t a) {
-  return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0;
-}
-
 inline bool finite_nonneg(double x) { return x >= 0.0 && x <= 1.7976931348623157e308; }
 
 }  // namespace
@@ -163,7 +160,7 @@ extern "C" int s3x_pose_grad(const float* viewmatrix, const float* means3D,
   S3_REQUIRE(n >= 0, "s3x_pose_grad: n < 0");
   S3_REQUIRE(n <= kMaxRows, "s3x_pose_grad: n too large");
   S3_REQUIRE(out, "s3x_pose_grad: null out");
-  S3_REQUIRE(aligned(out, 8), "s3x_pose_grad: out must be 8-byte aligned");
+  S3_REQUIRE(s3::aligned(out, 8), "s3x_pose_grad: out must be 8-byte aligned");
   const bool has_cov = cov3D || d_cov3D, has_rot = rotations || d_rotations;
   S3_REQUIRE(has_cov != has_rot,
              "s3x_pose_grad: give either cov3D and d_cov3D or rotations and d_rotations");
@@ -178,15 +175,15 @@ extern "C" int s3x_pose_grad(const float* viewmatrix, const float* means3D,
     S3_REQUIRE(workspace && workspace_bytes >= s3x_pose_grad_workspace_bytes(n),
                "s3x_pose_grad: workspace of %zu bytes, %zu needed", workspace_bytes,
                s3x_pose_grad_workspace_bytes(n));
-    S3_REQUIRE(aligned(workspace, 8), "s3x_pose_grad: workspace must be 8-byte aligned");
+    S3_REQUIRE(s3::aligned(workspace, 8), "s3x_pose_grad: workspace must be 8-byte aligned");
     double* partials = static_cast<double*>(workspace);
     if (has_cov) {
-      S3_REQUIRE(aligned(cov3D, 8) && aligned(d_cov3D, 8),
+      S3_REQUIRE(s3::aligned(cov3D, 8) && s3::aligned(d_cov3D, 8),
                  "s3x_pose_grad: cov3D and d_cov3D must be 8-byte aligned");
       k_pose_grad<true><<<(unsigned)blocks, kThreads, 0, st>>>(
           viewmatrix, means3D, d_means3D, cov3D, d_cov3D, radii, n, partials, skipped);
     } else {
-      S3_REQUIRE(aligned(rotations, 16) && aligned(d_rotations, 16),
+      S3_REQUIRE(s3::aligned(rotations, 16) && s3::aligned(d_rotations, 16),
                  "s3x_pose_grad: rotations and d_rotations must be 16-byte aligned");
       k_pose_grad<false><<<(unsigned)blocks, kThreads, 0, st>>>(
           viewmatrix, means3D, d_means3D, rotations, d_rotations, radii, n, partials, skipped);
@@ -215,11 +212,11 @@ extern "C" int s3x_pose_step(double* T_WC, double* exp_avg, double* exp_avg_sq,
     S3_REQUIRE(hp->bias2_sqrt > 0.0 && hp->bias2_sqrt <= 1.0,
                "s3x_pose_step: bias2_sqrt must be in (0, 1]");
     S3_REQUIRE(exp_avg && exp_avg_sq, "s3x_pose_step: null moments");
-    S3_REQUIRE(aligned(exp_avg, 8) && aligned(exp_avg_sq, 8) && aligned(grad, 8),
+    S3_REQUIRE(s3::aligned(exp_avg, 8) && s3::aligned(exp_avg_sq, 8) && s3::aligned(grad, 8),
                "s3x_pose_step: grad and the moments must be 8-byte aligned");
   }
   S3_REQUIRE(T_WC && proj_t && viewmatrix && projmatrix && campos, "s3x_pose_step: null argument");
-  S3_REQUIRE(aligned(T_WC, 8), "s3x_pose_step: T_WC must be 8-byte aligned");
+  S3_REQUIRE(s3::aligned(T_WC, 8), "s3x_pose_step: T_WC must be 8-byte aligned");
   const s3x::PoseAdam p{hp->lr_translation, hp->lr_rotation, hp->beta1, hp->beta2, hp->eps,
                         hp->bias1, hp->bias2_sqrt, hp->render_scale};
   k_pose_step<<<1, 64, 0, s3::as_stream(stream)>>>(T_WC, exp_avg, exp_avg_sq, grad, p, proj_t,

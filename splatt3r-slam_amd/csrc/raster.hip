@@ -25,6 +25,7 @@
 #include "device_util.hpp"
 #include "host_wait.hpp"
 #include "gsr.h"
+#include "radix_pass.hpp"
 #include "raster_math.hpp"
 
 using namespace gsr;
@@ -361,112 +362,19 @@ k_preprocess(int64_t P, Cam cam, const float* __restrict__ means,
 //   tile sort    the instances by tile id (11 bits at 960x540 -> 6 + 5).
 //
 // Each pass: k_rs_hist (digit counts of every 4096-item segment ->
-// hist[digit][segment]) -> k_row_scan (one wave per digit row, exclusive
-// offsets in place, row total) -> k_rs_scatter: per-wave digit counts in
-// LDS, the segment's items ranked within each 64-item window by a ballot
-// match on the digit (stable by construction), staged in LDS in digit order
-// and written out as runs of consecutive addresses (a random scatter of
-// single words would cost one partial-line write-back per item).
+// hist[digit][segment]) -> k_row_scan (one workgroup per digit row,
+// exclusive offsets in place, row total) -> k_rs_scatter (stable, LDS-staged).
+// The bodies are radix_pass.hpp's, the scans and wave primitives
+// wave_scan.hpp's; the keys are held as uint32 whatever their stored width.
 
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ uint64_t lanemask_lt(int lane) { return (1ull << lane) - 1ull; }
-
-// lanes of `active` holding the same `bits`-bit value as this lane
-__device__ __forceinline__ uint64_t match_peers(uint32_t d, bool active, int bits) {
-  uint64_t peers = __ballot(active);
-  for (int b = 0; b < bits; ++b) {
-    const bool set = (d >> b) & 1u;
-    const uint64_t m = __ballot(active && set);
-    peers &= set ? m : ~m;
-  }
-  return peers;
-}
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
-// exclusive scan of one value per thread across the workgroup; total too
-template <int NT>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_w,
-                                                    uint32_t* total = nullptr) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const uint32_t inc = wave_incl_scan(v, lane);
-  if (lane == 63) s_w[w] = inc;
-  __syncthreads();
-  uint32_t base = 0, all = 0;
-#pragma unroll
-  for (int k = 0; k < NT / 64; ++k) {
-    base += k < w ? s_w[k] : 0u;
-    all += s_w[k];
-  }
-  __syncthreads();
-  if (total) *total = all;
-  return base + inc - v;
-}
-
-// Per row: exclusive scan over `cols` columns in place, row total to
-// tot[row].  One workgroup per row; wave w owns a contiguous quarter of the
-// columns: quarter totals first, then the scan with the quarter's carry-in.
 __global__ void __launch_bounds__(kThreads)
 k_row_scan(uint32_t* __restrict__ hist, int64_t cols, uint32_t* __restrict__ tot) {
-  constexpr int NW = kThreads / 64, kCh = 8;
-  __shared__ uint32_t s_q[NW];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t* h = hist + (size_t)blockIdx.x * cols;
-  const int64_t per = (cols + NW - 1) / NW;
-  const int64_t q0 = min(cols, (int64_t)w * per), q1 = min(cols, q0 + per);
-  uint32_t sum = 0;
-  for (int64_t c0 = q0; c0 < q1; c0 += kCh * 64) {
-    uint32_t v[kCh];
-#pragma unroll
-    for (int j = 0; j < kCh; ++j) {
-      const int64_t c = c0 + j * 64 + lane;
-      v[j] = c < q1 ? h[c] : 0u;
-    }
-#pragma unroll
-    for (int j = 0; j < kCh; ++j) sum += v[j];
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-  if (lane == 0) s_q[w] = sum;
-  __syncthreads();
-  uint32_t carry = 0, all = 0;
-#pragma unroll
-  for (int k = 0; k < NW; ++k) {
-    carry += k < w ? s_q[k] : 0u;
-    all += s_q[k];
-  }
-  for (int64_t c0 = q0; c0 < q1; c0 += kCh * 64) {
-    uint32_t v[kCh];
-#pragma unroll
-    for (int j = 0; j < kCh; ++j) {
-      const int64_t c = c0 + j * 64 + lane;
-      v[j] = c < q1 ? h[c] : 0u;
-    }
-#pragma unroll
-    for (int j = 0; j < kCh; ++j) {
-      const int64_t c = c0 + j * 64 + lane;
-      const uint32_t inc = wave_incl_scan(v[j], lane);
-      if (c < q1) h[c] = carry + inc - v[j];
-      carry += __shfl(inc, 63, 64);
-    }
-  }
-  if (threadIdx.x == 0) tot[blockIdx.x] = all;
+  s3::radix_row_scan<kThreads, 8>(hist, cols, tot);
 }
 
 // digit of a key: (min(key - kmin, span) >> shift) & mask
 struct Digit {
+  static constexpr int max_bits = kMaxDigitBits;
   uint32_t kmin, span;
   int shift, bits;
   // device (kmin, span) of the sync-free forward (gsr_forward_deferred);
@@ -491,137 +399,20 @@ __device__ __forceinline__ int64_t live_n(int64_t n, const uint32_t* dn) {
 
 template <typename K>
 __global__ void __launch_bounds__(kSortThreads)
-k_rs_hist(int64_t n, const K* __restrict__ keys, Digit dg_in, int64_t nseg,
+k_rs_hist(int64_t n, const K* __restrict__ keys, Digit dg, int64_t nseg,
           uint32_t* __restrict__ hist, const uint32_t* __restrict__ dn) {
-  __shared__ uint32_t cnt[kMaxBins];
-  const Digit dg = dg_in.live();
-  n = live_n(n, dn);
-  const int bins = 1 << dg.bits;
-  for (int d = threadIdx.x; d < bins; d += kSortThreads) cnt[d] = 0u;
-  __syncthreads();
-  const int64_t s = blockIdx.x;
-  const int64_t i0 = s * kSegItems;
-  uint32_t key[kSortPerLane];
-#pragma unroll
-  for (int j = 0; j < kSortPerLane; ++j) {
-    const int64_t i = i0 + j * kSortThreads + threadIdx.x;
-    key[j] = i < n ? (uint32_t)keys[i] : 0u;
-  }
-#pragma unroll
-  for (int j = 0; j < kSortPerLane; ++j) {
-    // counts do not depend on the order: one LDS atomic per item (a ballot
-    // match per window costs a VALU op per digit bit)
-    if (i0 + j * kSortThreads + threadIdx.x < n) atomicAdd(&cnt[dg(key[j])], 1u);
-  }
-  __syncthreads();
-  for (int d = threadIdx.x; d < bins; d += kSortThreads) hist[(size_t)d * nseg + s] = cnt[d];
+  s3::radix_hist<kSortThreads, kSortPerLane, K, uint32_t>(live_n(n, dn), keys, dg.live(), nseg,
+                                                          hist);
 }
 
-// One segment of kSegItems items: wave w owns items [w * 512, (w + 1) *
-// 512) of it, in 8 windows of 64.
 template <typename K, typename V>
 __global__ void __launch_bounds__(kSortThreads)
 k_rs_scatter(int64_t n, const K* __restrict__ kin, const V* __restrict__ vin,
-             K* __restrict__ kout, V* __restrict__ vout, Digit dg_in, int64_t nseg,
+             K* __restrict__ kout, V* __restrict__ vout, Digit dg, int64_t nseg,
              const uint32_t* __restrict__ hist, const uint32_t* __restrict__ tot,
              const uint32_t* __restrict__ dn) {
-  constexpr int NW = kSortThreads / 64;
-  const Digit dg = dg_in.live();
-  n = live_n(n, dn);
-  __shared__ uint32_t cnt[NW][kMaxBins];  // per-wave counts -> local slots
-  __shared__ uint32_t gdelta[kMaxBins];   // global slot - local slot, per digit
-  __shared__ uint32_t s_w[NW];
-  __shared__ K sk[kSegItems];
-  __shared__ V sv[kSegItems];
-  const int bins = 1 << dg.bits;
-  for (int d = threadIdx.x; d < NW * kMaxBins; d += kSortThreads) (&cnt[0][0])[d] = 0u;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t s = blockIdx.x;
-  const int64_t seg0 = s * kSegItems;
-  const int64_t base_w = seg0 + (int64_t)w * 64 * kSortPerLane;
-  uint32_t key[kSortPerLane];
-  V val[kSortPerLane];
-  // phase A: every load issued first, then digits, window matches and
-  // per-wave counts
-#pragma unroll
-  for (int j = 0; j < kSortPerLane; ++j) {
-    const int64_t i = base_w + j * 64 + lane;
-    key[j] = i < n ? (uint32_t)kin[i] : 0u;
-    // vin == nullptr: the item's own index (first pass of the depth sort)
-    val[j] = i < n ? (vin ? vin[i] : (V)i) : V(0);
-  }
-#pragma unroll
-  for (int j = 0; j < kSortPerLane; ++j)   // counts: order-free, one LDS atomic per item
-    if (base_w + j * 64 + lane < n) atomicAdd(&cnt[w][dg(key[j])], 1u);
-  __syncthreads();
-  // phase B: local slots (digit-major within the segment) and the global
-  // offset of each digit's run; bins <= 2 * kSortThreads
-  {
-    constexpr int PER = kMaxBins / kSortThreads;
-    uint32_t tb[PER], gt[PER], lsum = 0, gsum = 0;
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int d = threadIdx.x * PER + q;
-      tb[q] = 0;
-      gt[q] = 0;
-      if (d < bins) {
-#pragma unroll
-        for (int k = 0; k < NW; ++k) tb[q] += cnt[k][d];
-        gt[q] = tot[d];
-      }
-      lsum += tb[q];
-      gsum += gt[q];
-    }
-    uint32_t lbase = block_excl_scan<kSortThreads>(lsum, s_w);
-    uint32_t gbase = block_excl_scan<kSortThreads>(gsum, s_w);
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int d = threadIdx.x * PER + q;
-      if (d < bins) {
-        gdelta[d] = gbase + hist[(size_t)d * nseg + s] - lbase;
-        uint32_t b = lbase;
-#pragma unroll
-        for (int k = 0; k < NW; ++k) {
-          const uint32_t c = cnt[k][d];
-          cnt[k][d] = b;
-          b += c;
-        }
-      }
-      lbase += tb[q];
-      gbase += gt[q];
-    }
-  }
-  __syncthreads();
-  // phase C: local slot = wave's running slot + rank among equal digits in
-  // the window; stage key and value there
-#pragma unroll
-  for (int j = 0; j < kSortPerLane; ++j) {
-    const bool ok = base_w + j * 64 + lane < n;
-    const uint32_t d = dg(key[j]);
-    const uint64_t peers = match_peers(d, ok, dg.bits);
-    if (ok) {
-      const uint32_t b = cnt[w][d];
-      const uint32_t lp = b + (uint32_t)__popcll(peers & lanemask_lt(lane));
-      if ((peers >> lane) == 1ull) cnt[w][d] = b + (uint32_t)__popcll(peers);
-      sk[lp] = (K)key[j];
-      sv[lp] = val[j];
-    }
-    wave_lds_sync();
-  }
-  __syncthreads();
-  // phase D: runs of equal digits go to consecutive global slots
-  const int m = (int)min<int64_t>(kSegItems, n - seg0);
-#pragma unroll
-  for (int j = 0; j < kSortPerLane; ++j) {
-    const int lp = j * kSortThreads + threadIdx.x;
-    if (lp < m) {
-      const K k = sk[lp];
-      const uint32_t gp = (uint32_t)lp + gdelta[dg((uint32_t)k)];
-      if (kout) kout[gp] = k;
-      vout[gp] = sv[lp];
-    }
-  }
+  s3::radix_scatter<kSortThreads, kSortPerLane, K, uint32_t>(live_n(n, dn), kin, vin, kout, vout,
+                                                             dg.live(), nseg, hist, tot);
 }
 
 __device__ __forceinline__ uint32_t dup_count(const uint4 d) {
@@ -662,15 +453,7 @@ k_order_gather(int64_t P, const uint32_t* __restrict__ order, const uint4* __res
 // exclusive scan of the segment counts in place (one workgroup)
 __global__ void __launch_bounds__(1024) k_seg_scan(uint32_t* __restrict__ cnt_seg, int64_t nseg) {
   __shared__ uint32_t s_w[16];
-  uint32_t carry = 0;
-  for (int64_t c0 = 0; c0 < nseg; c0 += 1024) {
-    const int64_t c = c0 + threadIdx.x;
-    const uint32_t v = c < nseg ? cnt_seg[c] : 0u;
-    uint32_t total = 0;
-    const uint32_t ex = block_excl_scan<1024>(v, s_w, &total);
-    if (c < nseg) cnt_seg[c] = carry + ex;
-    carry += total;
-  }
+  s3::block_excl_add_array<1024>(cnt_seg, nseg, s_w);
 }
 
 // Instances in depth order.  Each wave owns kDupRanks consecutive depth
@@ -721,7 +504,7 @@ k_duplicate(int64_t P, int gx, const uint32_t* __restrict__ order,
     const int rw = max(1, (int)(d.y & 0xFFFFu));
     const bool use_mask = rw * (int)(d.y >> 16) <= 64;
     const uint64_t mask = (uint64_t)d.z | ((uint64_t)d.w << 32);
-    const uint32_t inc = wave_incl_scan(cnt, lane);
+    const uint32_t inc = s3::wave_incl_add(cnt, lane);
     const uint32_t start = running + inc - cnt;
     const uint32_t lo = running;
     const uint32_t hi = running + __shfl(inc, 63, 64);
@@ -748,14 +531,14 @@ k_duplicate(int64_t P, int gx, const uint32_t* __restrict__ order,
           }
         }
       }
-      wave_lds_sync();
+      s3::wave_lds_sync();
       // cap: the instance capacity of the sync-free forward (instances past
       // it are dropped and the frame is flagged by k_red_finalize)
       for (uint32_t t = lane; t < c1 - c0 && c0 + t < cap; t += 64) {
         keys[c0 + t] = sk[t];
         vals[c0 + t] = sv[t];
       }
-      wave_lds_sync();
+      s3::wave_lds_sync();
     }
   }
 }
@@ -989,7 +772,7 @@ k_tile_scan(int ntiles, uint32_t* __restrict__ cursor, uint2* __restrict__ range
     const int c = c0 + threadIdx.x;
     const uint32_t v = c < ntiles ? cursor[c] : 0u;
     uint32_t total = 0;
-    const uint32_t ex = block_excl_scan<1024>(v, s_w, &total);
+    const uint32_t ex = s3::block_excl_add<1024>(v, s_w, &total);
     if (c < ntiles) {
       const uint32_t off = carry + ex;
       cursor[c] = off;
@@ -1101,13 +884,13 @@ __device__ __forceinline__ void ts_rank(TsLds& t, const TsPass& ps, const Digit&
     if (j < ipt) {
       const bool ok = base_w + j * 64 + lane < m;
       const uint32_t d = ts_digit(ps, dg, key[j], val[j]);
-      const uint64_t peers = match_peers(d, ok, ps.bits);
+      const uint64_t peers = s3::match_peers(d, ok, ps.bits);
       if (ok) {
         const uint32_t b = t.cnt[w][d];
-        put(j, b + (uint32_t)__popcll(peers & lanemask_lt(lane)));
+        put(j, b + (uint32_t)__popcll(peers & s3::lanemask_lt(lane)));
         if ((peers >> lane) == 1ull) t.cnt[w][d] = b + (uint32_t)__popcll(peers);
       }
-      wave_lds_sync();
+      s3::wave_lds_sync();
     }
   }
 }
@@ -1126,7 +909,7 @@ __device__ __forceinline__ void ts_offsets(TsLds& t, bool scan) {
     for (int k = 0; k < kTSWaves; ++k) tot += t.cnt[k][d];
   }
   uint32_t b = 0;
-  if (scan) b = block_excl_scan<kTSThreads>(d < 256 ? tot : 0u, t.w);
+  if (scan) b = s3::block_excl_add<kTSThreads>(d < 256 ? tot : 0u, t.w);
   if (d < 256) {
     if (!scan) b = t.run[d];
 #pragma unroll
@@ -1297,7 +1080,7 @@ k_tile_sort(int ntiles, const uint2* __restrict__ ranges, uint32_t* __restrict__
 #pragma unroll
         for (int k = 0; k < kTSWaves; ++k) tot += t.cnt[k][d];
       }
-      const uint32_t b = block_excl_scan<kTSThreads>(d < 256 ? tot : 0u, t.w);
+      const uint32_t b = s3::block_excl_add<kTSThreads>(d < 256 ? tot : 0u, t.w);
       if (d < 256) t.run[d] = b;
     }
     __syncthreads();

@@ -16,10 +16,9 @@
 //    keep the lower centroid index.
 #include <cfloat>
 
-#include <hipcub/hipcub.hpp>
-
 #include "common.hpp"
 #include "s3q.h"
+#include "wave_scan.hpp"
 
 namespace {
 
@@ -424,9 +423,8 @@ AggWs carve_agg(void* base, int m, size_t* total = nullptr) {
 __global__ void __launch_bounds__(kAggThreads)
 k_asmk_sort(const int64_t* __restrict__ words, int m, int k, int32_t* __restrict__ out_words,
             int32_t* __restrict__ out_count, AggWs w) {
-  typedef hipcub::BlockScan<int, kAggThreads> Scan;
   __shared__ uint64_t key[kAggMax];
-  __shared__ typename Scan::TempStorage scan_tmp;
+  __shared__ uint32_t s_w[kAggThreads / 64];
   int L = 1;
   while (L < m) L <<= 1;
   for (int i = threadIdx.x; i < L; i += kAggThreads)
@@ -453,8 +451,17 @@ k_asmk_sort(const int64_t* __restrict__ words, int m, int k, int32_t* __restrict
     const int i = base + t;
     hd[t] = (i < m && (i == 0 || (key[i] >> 16) != (key[i - 1] >> 16))) ? 1 : 0;
   }
-  int total = 0;
-  Scan(scan_tmp).ExclusiveSum(hd, hd, total);
+  uint32_t heads = 0, all = 0;
+#pragma unroll
+  for (int t = 0; t < kAggItems; ++t) heads += (uint32_t)hd[t];
+  int run = (int)s3::block_excl_add<kAggThreads>(heads, s_w, &all);
+#pragma unroll
+  for (int t = 0; t < kAggItems; ++t) {
+    const int h = hd[t];
+    hd[t] = run;
+    run += h;
+  }
+  const int total = (int)all;
 #pragma unroll
   for (int t = 0; t < kAggItems; ++t) {
     const int i = base + t;

@@ -19,71 +19,19 @@
 // The emit reads the stored code and does not recompute the decision: the
 // statistics (12 B a row) and the two exps and the sigmoid are paid once.
 // Rows are 56 bytes: seven 8-byte accesses per row, as in splat_opt.hip.
+#include "arg_check.hpp"
 #include "common.hpp"
 #include "s3d.h"
 #include "splat_density_math.hpp"
+#include "wave_scan.hpp"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kRow = s3d::kRow;
 constexpr int kScanThreads = 1024;
-static_assert(kRow % 2 == 0, "a row is whole float2s");
 // origin holds a row index as int32
 constexpr int64_t kMaxRows = ((int64_t)1 << 31) - 1;
-
-__device__ __forceinline__ void load_row(const float* __restrict__ base, int64_t i,
-                                         float (&r)[kRow]) {
-  const float2* p = reinterpret_cast<const float2*>(base + i * kRow);
-#pragma unroll
-  for (int k = 0; k < kRow / 2; ++k) {
-    const float2 t = p[k];
-    r[2 * k] = t.x;
-    r[2 * k + 1] = t.y;
-  }
-}
-
-__device__ __forceinline__ void store_row(float* __restrict__ base, int64_t i,
-                                          const float (&r)[kRow]) {
-  float2* p = reinterpret_cast<float2*>(base + i * kRow);
-#pragma unroll
-  for (int k = 0; k < kRow / 2; ++k) p[k] = make_float2(r[2 * k], r[2 * k + 1]);
-}
-
-__device__ __forceinline__ void zero_row(float* __restrict__ base, int64_t i) {
-  float2* p = reinterpret_cast<float2*>(base + i * kRow);
-#pragma unroll
-  for (int k = 0; k < kRow / 2; ++k) p[k] = make_float2(0.0f, 0.0f);
-}
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
-
-// Block-wide exclusive scan of one value per thread (NT threads, NT / 64
-// waves); *total receives the block's sum.
-template <int NT>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t* s_w, uint32_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  constexpr int NW = NT / 64;
-  const uint32_t incl = wave_incl_scan(x, lane);
-  if (lane == 63) s_w[wave] = incl;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) {
-    if (w < wave) base += s_w[w];
-    tot += s_w[w];
-  }
-  __syncthreads();
-  if (total) *total = tot;
-  return base + incl - x;
-}
 
 // alive in the low half, growing in the high half: a block holds at most 256
 // of either, so the packed sums of one block never carry across.
@@ -118,13 +66,13 @@ k_density_classify(const float* __restrict__ rows14, int64_t n,
   uint32_t f = 0;
   if (i < n) {
     float r[kRow];
-    load_row(rows14, i, r);
+    s3w::load_row(rows14, i, r);
     const int code = s3d::decide(r, grad_accum[i], denom[i], max_radii[i], p);
     codes[i] = (uint8_t)code;
     f = pack_flags(code);
   }
   uint32_t tot = 0;
-  block_excl_scan<kThreads>(f, s_w, &tot);
+  s3::block_excl_add<kThreads>(f, s_w, &tot);
   if (threadIdx.x == 0) {
     b_alive[blockIdx.x] = tot & 0xffffu;
     b_grow[blockIdx.x] = tot >> 16;
@@ -144,8 +92,8 @@ k_density_scan(uint32_t* __restrict__ b_alive, uint32_t* __restrict__ b_grow, in
     const uint32_t a = c < nblk ? b_alive[c] : 0u;
     const uint32_t g = c < nblk ? b_grow[c] : 0u;
     uint32_t tot_a = 0, tot_g = 0;
-    const uint32_t ea = block_excl_scan<kScanThreads>(a, s_w, &tot_a);
-    const uint32_t eg = block_excl_scan<kScanThreads>(g, s_w, &tot_g);
+    const uint32_t ea = s3::block_excl_add<kScanThreads>(a, s_w, &tot_a);
+    const uint32_t eg = s3::block_excl_add<kScanThreads>(g, s_w, &tot_g);
     if (c < nblk) {
       b_alive[c] = carry_a + ea;
       b_grow[c] = carry_g + eg;
@@ -181,7 +129,7 @@ k_density_emit(const float* __restrict__ rows14, const float* __restrict__ exp_a
   if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0u;
   const int code = i < n ? (int)codes[i] : s3d::kPrune;
   const uint32_t f = pack_flags(code);
-  const uint32_t ex = block_excl_scan<kThreads>(f, s_w, nullptr);  // both barriers: s_cnt is set
+  const uint32_t ex = s3::block_excl_add<kThreads>(f, s_w, nullptr);  // both barriers: s_cnt is set
   if (code != s3d::kPrune) {
     const int64_t alive_before = (int64_t)b_alive[blockIdx.x] + (ex & 0xffffu);
     const int64_t grow_before = (int64_t)b_grow[blockIdx.x] + (ex >> 16);
@@ -189,29 +137,29 @@ k_density_emit(const float* __restrict__ rows14, const float* __restrict__ exp_a
     const int64_t off = alive_before + (grow_before < budget ? grow_before : budget);
     const bool grows = code >= s3d::kClone && grow_before < budget;
     float r[kRow], m[kRow];
-    load_row(rows14, i, r);
+    s3w::load_row(rows14, i, r);
     if (grows && code == s3d::kSplit) {
       float c[kRow];
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
         s3d::split_child(r, i, pass, (uint32_t)k, seed, c);
-        store_row(out_rows, off + k, c);
-        zero_row(out_m, off + k);
-        zero_row(out_v, off + k);
+        s3w::store_row(out_rows, off + k, c);
+        s3w::zero_row(out_m, off + k);
+        s3w::zero_row(out_v, off + k);
         origin[off + k] = ~(int32_t)i;
       }
       atomicAdd(&s_cnt[1], 1u);
     } else {
-      store_row(out_rows, off, r);
-      load_row(exp_avg, i, m);
-      store_row(out_m, off, m);
-      load_row(exp_avg_sq, i, m);
-      store_row(out_v, off, m);
+      s3w::store_row(out_rows, off, r);
+      s3w::load_row(exp_avg, i, m);
+      s3w::store_row(out_m, off, m);
+      s3w::load_row(exp_avg_sq, i, m);
+      s3w::store_row(out_v, off, m);
       origin[off] = (int32_t)i;
       if (grows) {
-        store_row(out_rows, off + 1, r);
-        zero_row(out_m, off + 1);
-        zero_row(out_v, off + 1);
+        s3w::store_row(out_rows, off + 1, r);
+        s3w::zero_row(out_m, off + 1);
+        s3w::zero_row(out_v, off + 1);
         origin[off + 1] = ~(int32_t)i;
         atomicAdd(&s_cnt[0], 1u);
       }
@@ -231,15 +179,6 @@ k_density_reset_opacity(float* __restrict__ rows14, float* __restrict__ exp_avg,
   if (l > logit_cap) rows14[i * kRow + 6] = logit_cap;   // a NaN logit stays, as torch.minimum
   exp_avg[i * kRow + 6] = 0.0f;
   exp_avg_sq[i * kRow + 6] = 0.0f;
-}
-
-inline bool aligned(const void* p, uintptr_t a) {
-  return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0;
-}
-
-inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return x < y + nb && y < x + na;
 }
 
 struct Workspace {
@@ -308,19 +247,19 @@ extern "C" int s3d_densify(const float* rows14, const float* exp_avg, const floa
     s3::set_error("s3d_densify: workspace of %zu bytes, %zu needed", workspace_bytes, w.bytes);
     return S3_ERR_WORKSPACE;
   }
-  S3_REQUIRE(aligned(workspace, 4), "s3d_densify: workspace must be 4-byte aligned");
-  S3_REQUIRE(aligned(rows14, 8) && aligned(exp_avg, 8) && aligned(exp_avg_sq, 8) &&
-                 aligned(out_rows, 8) && aligned(out_exp_avg, 8) && aligned(out_exp_avg_sq, 8),
+  S3_REQUIRE(s3::aligned(workspace, 4), "s3d_densify: workspace must be 4-byte aligned");
+  S3_REQUIRE(s3::aligned(rows14, 8) && s3::aligned(exp_avg, 8) && s3::aligned(exp_avg_sq, 8) &&
+                 s3::aligned(out_rows, 8) && s3::aligned(out_exp_avg, 8) && s3::aligned(out_exp_avg_sq, 8),
              "s3d_densify: row arrays must be 8-byte aligned");
   const size_t in_b = (size_t)n * kRow * sizeof(float), out_b = (size_t)cap * kRow * sizeof(float);
   const float* ins[3] = {rows14, exp_avg, exp_avg_sq};
   float* outs[3] = {out_rows, out_exp_avg, out_exp_avg_sq};
   for (int a = 0; a < 3; ++a) {
     for (int b = 0; b < 3; ++b)
-      S3_REQUIRE(!overlap(outs[a], out_b, ins[b], in_b),
+      S3_REQUIRE(!s3::overlap(outs[a], out_b, ins[b], in_b),
                  "s3d_densify: an output overlaps an input");
     for (int b = a + 1; b < 3; ++b)
-      S3_REQUIRE(!overlap(outs[a], out_b, outs[b], out_b), "s3d_densify: outputs overlap");
+      S3_REQUIRE(!s3::overlap(outs[a], out_b, outs[b], out_b), "s3d_densify: outputs overlap");
   }
   const int64_t nblk = s3::cdiv(n, kThreads);
   hipStream_t st = s3::as_stream(stream);

@@ -20,6 +20,7 @@ namespace s3w {
 constexpr float kC0 = 0.28209479177387814f;
 constexpr int kRowFloats = 17;    // x y z nx ny nz f_dc[3] opacity scale[3] rot[4]
 constexpr int kRow14Floats = 14;  // x y z f_dc[3] opacity scale[3] rot[4]
+static_assert(kRow14Floats % 2 == 0, "a 14-float row is whole float2s");
 // Cyclic Jacobi converges quadratically once the off-diagonal part is small:
 // float32 3x3 matrices are converged after 4 sweeps (errors against float64
 // no longer change), the fifth is margin.  The kernel takes
@@ -228,6 +229,31 @@ S3W_HD void splat_unpack(const float (&r)[kRow14Floats], float (&mean)[3], float
 #pragma unroll
     for (int j = i; j < 3; ++j)
       cov[k++] = M[i][0] * M[j][0] + M[i][1] * M[j][1] + M[i][2] * M[j][2];
+}
+
+// A 14-float row as seven 8-byte accesses (rows are 56 B: 8-byte aligned).
+__device__ __forceinline__ void load_row(const float* __restrict__ base, int64_t i,
+                                         float (&r)[kRow14Floats]) {
+  const float2* p = reinterpret_cast<const float2*>(base + i * kRow14Floats);
+#pragma unroll
+  for (int k = 0; k < kRow14Floats / 2; ++k) {
+    const float2 t = p[k];
+    r[2 * k] = t.x;
+    r[2 * k + 1] = t.y;
+  }
+}
+
+__device__ __forceinline__ void store_row(float* __restrict__ base, int64_t i,
+                                          const float (&r)[kRow14Floats]) {
+  float2* p = reinterpret_cast<float2*>(base + i * kRow14Floats);
+#pragma unroll
+  for (int k = 0; k < kRow14Floats / 2; ++k) p[k] = make_float2(r[2 * k], r[2 * k + 1]);
+}
+
+__device__ __forceinline__ void zero_row(float* __restrict__ base, int64_t i) {
+  float2* p = reinterpret_cast<float2*>(base + i * kRow14Floats);
+#pragma unroll
+  for (int k = 0; k < kRow14Floats / 2; ++k) p[k] = make_float2(0.0f, 0.0f);
 }
 
 }  // namespace s3w

@@ -16,6 +16,7 @@
 // rows through LDS as one contiguous float4 run (k_map_to_splats), was not
 // built: it loads and stores every row of the run, the culled ones included,
 // which is what the sparse step exists to avoid.
+#include "arg_check.hpp"
 #include "common.hpp"
 #include "s3o.h"
 #include "splat_opt_math.hpp"
@@ -24,27 +25,8 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kRow = s3o::kRow;
-static_assert(kRow % 2 == 0, "a row is whole float2s");
 // a grid has at most 2^31 - 1 workgroups
 constexpr int64_t kMaxRows = (((int64_t)1 << 31) - 1) * kThreads;
-
-__device__ __forceinline__ void load_row(const float* __restrict__ base, int64_t i,
-                                         float (&r)[kRow]) {
-  const float2* p = reinterpret_cast<const float2*>(base + i * kRow);
-#pragma unroll
-  for (int k = 0; k < kRow / 2; ++k) {
-    const float2 t = p[k];
-    r[2 * k] = t.x;
-    r[2 * k + 1] = t.y;
-  }
-}
-
-__device__ __forceinline__ void store_row(float* __restrict__ base, int64_t i,
-                                          const float (&r)[kRow]) {
-  float2* p = reinterpret_cast<float2*>(base + i * kRow);
-#pragma unroll
-  for (int k = 0; k < kRow / 2; ++k) p[k] = make_float2(r[2 * k], r[2 * k + 1]);
-}
 
 __global__ void __launch_bounds__(kThreads)
 k_splat_activate(const float* __restrict__ rows14, int64_t n, float s,
@@ -54,7 +36,7 @@ k_splat_activate(const float* __restrict__ rows14, int64_t n, float s,
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (i >= n) return;
   float r[kRow];
-  load_row(rows14, i, r);
+  s3w::load_row(rows14, i, r);
   float mean[3], sh[3], op, sc[3], q[4];
   s3o::activate(r, s, mean, sh, op, sc, q);
 #pragma unroll
@@ -91,18 +73,14 @@ k_splat_adam(float* __restrict__ rows14, float* __restrict__ exp_avg,
     return;
   }
   float r[kRow], m[kRow], v[kRow];
-  load_row(rows14, i, r);
-  load_row(exp_avg, i, m);
-  load_row(exp_avg_sq, i, v);
+  s3w::load_row(rows14, i, r);
+  s3w::load_row(exp_avg, i, m);
+  s3w::load_row(exp_avg_sq, i, v);
   s3o::adam_row(r, m, v, hp.render_scale, dmean, dsh, dop, dsc, dq, hp.lr, hp.beta1, hp.beta2,
                 hp.eps, hp.bias1, hp.bias2_sqrt);
-  store_row(rows14, i, r);
-  store_row(exp_avg, i, m);
-  store_row(exp_avg_sq, i, v);
-}
-
-inline bool aligned(const void* p, uintptr_t a) {
-  return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0;
+  s3w::store_row(rows14, i, r);
+  s3w::store_row(exp_avg, i, m);
+  s3w::store_row(exp_avg_sq, i, v);
 }
 
 }  // namespace
@@ -118,8 +96,8 @@ extern "C" int s3o_activate(const float* rows14, int64_t n, float render_scale, 
   if (n == 0) return S3_OK;
   S3_REQUIRE(rows14 && means3D && shs && opacities && scales && rotations,
              "s3o_activate: null argument");
-  S3_REQUIRE(aligned(rows14, 8), "s3o_activate: rows14 must be 8-byte aligned");
-  S3_REQUIRE(aligned(rotations, 16), "s3o_activate: rotations must be 16-byte aligned");
+  S3_REQUIRE(s3::aligned(rows14, 8), "s3o_activate: rows14 must be 8-byte aligned");
+  S3_REQUIRE(s3::aligned(rotations, 16), "s3o_activate: rotations must be 16-byte aligned");
   k_splat_activate<<<(unsigned)s3::cdiv(n, kThreads), kThreads, 0, s3::as_stream(stream)>>>(
       rows14, n, render_scale, means3D, shs, opacities, scales, rotations);
   S3_LAUNCH_CHECK();
@@ -151,9 +129,9 @@ extern "C" int s3o_adam_step(float* rows14, float* exp_avg, float* exp_avg_sq, i
   S3_REQUIRE(rows14 && exp_avg && exp_avg_sq, "s3o_adam_step: null parameter or moment rows");
   S3_REQUIRE(d_means3D && d_shs && d_opacities && d_scales && d_rotations,
              "s3o_adam_step: null gradient");
-  S3_REQUIRE(aligned(rows14, 8) && aligned(exp_avg, 8) && aligned(exp_avg_sq, 8),
+  S3_REQUIRE(s3::aligned(rows14, 8) && s3::aligned(exp_avg, 8) && s3::aligned(exp_avg_sq, 8),
              "s3o_adam_step: rows14, exp_avg and exp_avg_sq must be 8-byte aligned");
-  S3_REQUIRE(aligned(d_rotations, 16), "s3o_adam_step: d_rotations must be 16-byte aligned");
+  S3_REQUIRE(s3::aligned(d_rotations, 16), "s3o_adam_step: d_rotations must be 16-byte aligned");
   k_splat_adam<<<(unsigned)s3::cdiv(n, kThreads), kThreads, 0, s3::as_stream(stream)>>>(
       rows14, exp_avg, exp_avg_sq, n, d_means3D, d_shs, d_opacities, d_scales, d_rotations,
       radii, *hp, skipped);

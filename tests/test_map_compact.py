@@ -78,8 +78,9 @@ ORIGINS = ((0.0, 0.0, 0.0), (-1.37, 2.21, -0.53))
 # sums take one per 256 rows, so 257 already has two), and 2,097,153 the first
 # at which the top scan over those workgroups' sums (1,024 per trip) takes a
 # second trip; its group of 20,000 rows is past the 16,384 at which a thread of
-# the long-group pass takes a second chunk.
-SIZES = (1, 2, 257, 2049, 4099, 2097153)
+# the long-group pass takes a second chunk.  2,047 and 2,048 are one row short
+# of a sort segment and exactly one segment.
+SIZES = (1, 2, 257, 2047, 2048, 2049, 4099, 2097153)
 
 
 def _sizes_of_groups(n, rng):

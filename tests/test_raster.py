@@ -238,15 +238,16 @@ def _restage(sc, z):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("binning", ["tile", "global"])
-@pytest.mark.parametrize("case", ["plane", "two_depths", "wide_range", "all_culled", "tail_4097",
-                                  "tail_8193", "tiles_3600", "tiles_8160", "tiles_8832",
+@pytest.mark.parametrize("case", ["plane", "two_depths", "wide_range", "all_culled",
+                                  "full_4096", "tail_4097", "tail_8193", "tiles_3600", "tiles_8160", "tiles_8832",
                                   "big_splats", "ragged_1x1", "one_tile_20k", "one_tile_20k_plane"])
 def test_hip_binning_edge_cases_bitexact_vs_oracle(case, binning):
     """Both forward binnings (the global depth + tile sorts of raster.hip
     "sorting", the default, and "per-tile binning"): equal depths (ties resolved
     by Gaussian index: the per-tile sort's index passes), a 1-2 pass key
-    width, a 4-pass key width, nothing visible (R = 0), segment tails (4096
-    and 8192 items), tile ids of 12, 13 and 14 bits (8,832 tiles: past the
+    width, a 4-pass key width, nothing visible (R = 0), exactly one full
+    segment (4096 items), segment tails (4096 and 8192 items), tile ids of
+    12, 13 and 14 bits (8,832 tiles: past the
     per-tile path's 8,192, so the global path runs), splats whose rect
     exceeds the 64-tile mask (plain rect enumeration), a ragged 1-tile image,
     and ~20k instances in one tile (past the 16,384 sorted in LDS: the
@@ -257,6 +258,8 @@ def test_hip_binning_edge_cases_bitexact_vs_oracle(case, binning):
     P, H, W, fx = 3000, 48, 64, 60.0
     if case.startswith("one_tile_20k"):
         P, H, W, fx = 20000, 16, 16, 15.0
+    if case == "full_4096":
+        P = 4096
     if case == "tail_4097":
         P = 4097
     if case == "tail_8193":

@@ -175,11 +175,17 @@ def test_oracle_asmk_self_match_scores_one_per_word():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("k", [1, 5])
-def test_hip_asmk_aggregate_matches_oracle(k):
+@pytest.mark.parametrize("n,k,C", [pytest.param(300, 1, 4096, id="1"),
+                                   pytest.param(300, 5, 4096, id="5"),
+                                   pytest.param(1, 1, 256, id="one_pair"),
+                                   pytest.param(1024, 4, 256, id="full_4096")])
+def test_hip_asmk_aggregate_matches_oracle(n, k, C):
+    """Also the least and the most (word, descriptor) pairs the sort workgroup
+    takes: n k = 1, and n k = 4096 (1,024 threads of 4 items, every one live)
+    over 256 words, so the segments are many descriptors long."""
     from oracle.retrieval_ref import asmk_aggregate as ref_agg, quantize
     from splatt3r_amd.retrieval_database import asmk_aggregate
-    cen, f = _asmk_case(1)
+    cen, f = _asmk_case(1, n=n, C=C)
     idx, _, _ = quantize(f, cen, k)
     w, c, n = asmk_aggregate(f.cuda(), idx.cuda(), cen.cuda())
     rw, rc = ref_agg(f.numpy(), idx.numpy(), cen.numpy())
