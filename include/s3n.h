@@ -180,7 +180,11 @@ void s3n_attention_set_variant(int variant);
 
 /* LayerNorm over the last dim C (eps), per group gamma/beta:
  * y = (x - mean) * rsqrt(var + eps) * gamma + beta.  x fp32 [rows, ldx];
- * out16 (fp16, ld16) and/or out32 (fp32, ld32) may be NULL. */
+ * out16 (fp16, ld16) and/or out32 (fp32, ld32) may be NULL.
+ * Requires C % 4 == 0, 4 <= C <= 2048, 1 <= groups <= S3N_MAX_GROUPS and
+ * ldx, ld32, ld16 multiples of 4 (anything else is S3_ERR_INVALID; rows == 0
+ * is a no-op).  x, gamma, beta and out32 pointers must be 16-byte aligned,
+ * out16 pointers 8-byte aligned: rows move as float4 / half4 vectors. */
 int s3n_layernorm(int rows, int C, int groups, const float* const* x, int64_t ldx,
                   const float* const* gamma, const float* const* beta, float eps,
                   void* const* out16, int64_t ld16, float* const* out32, int64_t ld32,

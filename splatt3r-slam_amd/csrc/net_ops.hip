@@ -15,7 +15,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kThreads = 256;
 
 // ------------------------------------------------------------ LayerNorm --
-// One wave per row; C <= 1024 (multiple of 4), held in registers.
+// One wave per row, held in registers: C <= 2048, a multiple of 4 (VPL float4
+// vectors per lane cover 256 * VPL columns; 1, 2, 3, 4 and 8 are instantiated).
+// Rows are read and written as 16-byte (fp16 output: 8-byte) vectors.
 struct LnP {
   int rows, C;
   const float* x[S3N_MAX_GROUPS];

@@ -2,7 +2,9 @@
 same op, on the same (fp16-rounded) inputs.  Tolerances are stated per test:
 fp16 operands with fp32 MFMA accumulation vs an fp32 matmul of the same
 fp16-rounded operands -> only accumulation-order differences (~1e-6 rel),
-plus one fp16 rounding when the kernel writes fp16."""
+plus one fp16 rounding when the kernel writes fp16.
+The six net_ops.hip kernels (LayerNorm, upsample, postprocess, cast, im2col,
+PRNG) are pinned at their edges against fp64 in tests/test_net_ops_edges.py."""
 import numpy as np
 import pytest
 import torch
