@@ -80,6 +80,7 @@ SOURCES = {
     "map_compact.hip": STRICT,
     "map_reanchor.hip": STRICT,
     "tsdf_mesh.hip": STRICT,
+    "nn_search.hip": STRICT,
 }
 
 

@@ -47,6 +47,34 @@ __device__ __forceinline__ uint32_t block_excl_add(uint32_t v, uint32_t* s_w,
   return base + inc - v;
 }
 
+// the same sum of one uint64 per thread (s_w: NT / 64 uint64 words)
+__device__ __forceinline__ uint64_t wave_incl_add64(uint64_t v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint64_t t = __shfl_up((unsigned long long)v, o, 64);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+
+template <int NT>
+__device__ __forceinline__ uint64_t block_excl_add64(uint64_t v, uint64_t* s_w,
+                                                     uint64_t* total = nullptr) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const uint64_t inc = wave_incl_add64(v, lane);
+  if (lane == 63) s_w[w] = inc;
+  __syncthreads();
+  uint64_t base = 0, all = 0;
+#pragma unroll
+  for (int k = 0; k < NT / 64; ++k) {
+    base += k < w ? s_w[k] : 0ull;
+    all += s_w[k];
+  }
+  __syncthreads();
+  if (total) *total = all;
+  return base + inc - v;
+}
+
 // exclusive running maximum (identity 0) likewise
 template <int NT>
 __device__ __forceinline__ uint32_t block_excl_max(uint32_t v, uint32_t* s_w,

@@ -29,6 +29,15 @@ reference's evaluate.py has no function for either: `write_splat_ply`,
 `read_splat_ply` and `save_gaussian_splats` (format and values: include/s3w.h
 s3w_map_to_splats).
 
+Geometry against ground truth has no counterpart either (the reference's
+scripts call `evo_ape tum gt est -as` for the trajectory and score no
+surface): `eval_reconstruction` (accuracy, completion, Chamfer distance,
+F-score over exact nearest neighbours on the device, splatt3r_amd/nn.py,
+include/s3k.h), `align_umeyama`, `read_traj`, `associate`, `eval_trajectory`
+(host float64; the quantity evo reports, parity with evo unpinned: it is not
+installed here) and `save_geometry_metrics` / `load_geometry_metrics`
+(DESIGN.md §6s).
+
 save_reconstruction's use_calib branch constrains points to their pixel
 rays first (evaluate.py:55-59).  save_traj's `intrinsics` branch calls
 `intrinsics.refine_pose_with_calibration(keyframe)` (evaluate.py:42), a
@@ -507,3 +516,231 @@ def eval_novel_view_renders(model, keyframes, K=None, gap=1, alpha_min=0.5):
     means = {k: float(np.mean([r[k] for r in rows])) for k in ("mse", "psnr", "ssim", "l1")} \
         if rows else {}
     return dict(rows=rows, means=means, skipped=skipped, empty=empty)
+
+
+# ------------------------------------------- geometry against ground truth ----
+def align_umeyama(src, dst, with_scale=True):
+    """(s, R, t) minimising sum |dst - (s R src + t)|^2 over similarities
+    (Umeyama 1991, with the determinant correction: R is a rotation, never a
+    reflection); s = 1 with with_scale=False.  src, dst: [n, 3], numpy
+    float64 throughout.  Raises ValueError for fewer than 3 points, mismatched
+    shapes, non-finite entries, or points whose cross-covariance has rank
+    below 2 (coincident or collinear: the rotation is not determined)."""
+    src, dst = np.asarray(src, np.float64), np.asarray(dst, np.float64)
+    if src.ndim != 2 or src.shape[1] != 3 or src.shape != dst.shape:
+        raise ValueError(f"align_umeyama: need two [n, 3] arrays, got {src.shape} and {dst.shape}")
+    n = len(src)
+    if n < 3:
+        raise ValueError(f"align_umeyama: need at least 3 points, got {n}")
+    if not (np.isfinite(src).all() and np.isfinite(dst).all()):
+        raise ValueError("align_umeyama: non-finite point")
+    mu_s, mu_d = src.mean(0), dst.mean(0)
+    xs, xd = src - mu_s, dst - mu_d
+    var_s = (xs ** 2).sum() / n
+    U, D, Vt = np.linalg.svd(xd.T @ xs / n)
+    if not (var_s > 0.0 and D[0] > 0.0 and D[1] > 1e-12 * D[0]):
+        raise ValueError("align_umeyama: degenerate points (coincident or collinear)")
+    S = np.ones(3)
+    if np.linalg.det(U) * np.linalg.det(Vt) < 0.0:
+        S[2] = -1.0
+    R = (U * S) @ Vt
+    s = float((D * S).sum() / var_s) if with_scale else 1.0
+    return s, R, mu_d - s * (R @ mu_s)
+
+
+def read_traj(path):
+    """Reader for the TUM-format files save_traj writes (`t x y z qx qy qz qw`
+    per line; `#` lines and empty lines skipped): (timestamps [n] float64,
+    poses [n, 7] float64)."""
+    ts, poses = [], []
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            p = line.split()
+            if not p or p[0].startswith("#"):
+                continue
+            if len(p) != 8:
+                raise ValueError(f"{path}:{ln}: expected 8 columns, got {len(p)}")
+            ts.append(float(p[0]))
+            poses.append([float(v) for v in p[1:]])
+    return np.asarray(ts, np.float64), np.asarray(poses, np.float64).reshape(-1, 7)
+
+
+def associate(ts_a, ts_b, max_dt=0.02):
+    """One-to-one pairing of two timestamp lists: every pair with
+    |a - b| <= max_dt is a candidate, candidates are taken nearest first
+    (ties: lower index in a, then in b) and a timestamp is used once.
+    Returns (ia, ib) int64 index arrays ordered by ia.  max_dt's default is
+    that of the TUM benchmark's associate.py as recalled, not a tuned value."""
+    ts_a, ts_b = np.asarray(ts_a, np.float64).reshape(-1), np.asarray(ts_b, np.float64).reshape(-1)
+    order = np.argsort(ts_b, kind="stable")
+    sb = ts_b[order]
+    cand = []
+    for i, a in enumerate(ts_a):
+        lo, hi = np.searchsorted(sb, a - max_dt, "left"), np.searchsorted(sb, a + max_dt, "right")
+        for j in order[lo:hi]:
+            d = abs(a - ts_b[j])
+            if d <= max_dt:
+                cand.append((d, i, int(j)))
+    cand.sort()
+    used_a, used_b, pairs = set(), set(), []
+    for _, i, j in cand:
+        if i not in used_a and j not in used_b:
+            used_a.add(i)
+            used_b.add(j)
+            pairs.append((i, j))
+    pairs.sort()
+    ia = np.asarray([p[0] for p in pairs], np.int64)
+    ib = np.asarray([p[1] for p in pairs], np.int64)
+    return ia, ib
+
+
+def _as_traj(x):
+    if isinstance(x, (str, pathlib.Path)):
+        return read_traj(x)
+    ts, poses = x
+    poses = np.asarray(poses, np.float64)
+    return np.asarray(ts, np.float64).reshape(-1), poses.reshape(len(poses), -1)
+
+
+def eval_trajectory(est, gt, with_scale=True, max_dt=0.02, align=True):
+    """Absolute trajectory error of the positions: est and gt are each a
+    TUM-format path or (timestamps [n], poses [n, >= 3]) with the position in
+    the first three columns.  Poses are paired by `associate`, est is aligned
+    to gt with `align_umeyama` (align=False: compared as given) and the error
+    of a pair is |gt - (s R est + t)|.  Returns rmse, mean, median, std
+    (population), min, max, n (pairs), scale, R, t: the quantity
+    `evo_ape tum gt est -as` reports (-a without scale for with_scale=False);
+    evo is not installed here, so parity with it is not pinned."""
+    (ts_e, p_e), (ts_g, p_g) = _as_traj(est), _as_traj(gt)
+    ia, ib = associate(ts_e, ts_g, max_dt)
+    if len(ia) == 0:
+        raise ValueError("eval_trajectory: no timestamps within max_dt of each other")
+    src, dst = p_e[ia, :3], p_g[ib, :3]
+    s, R, t = align_umeyama(src, dst, with_scale) if align else (1.0, np.eye(3), np.zeros(3))
+    e = np.sqrt(((dst - (s * (src @ R.T) + t)) ** 2).sum(1))
+    return dict(rmse=float(np.sqrt((e ** 2).mean())), mean=float(e.mean()),
+                median=float(np.median(e)), std=float(e.std()), min=float(e.min()),
+                max=float(e.max()), n=int(len(e)), scale=float(s), R=R, t=t)
+
+
+def apply_transform(points, transform):
+    """s R p + t of points [n, 3] (array or tensor) for transform = (s, R, t):
+    each coordinate as s ((R_k0 x + R_k1 y) + R_k2 z) + t_k in numpy float64,
+    rounded to float32 once.  Returns a float32 host array."""
+    s, R, t = transform
+    s, R, t = float(s), np.asarray(R, np.float64).reshape(3, 3), np.asarray(t, np.float64).reshape(3)
+    p = points.detach().cpu().numpy() if torch.is_tensor(points) else np.asarray(points)
+    p = p.reshape(-1, 3).astype(np.float64)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    out = np.stack([s * ((R[k, 0] * x + R[k, 1] * y) + R[k, 2] * z) + t[k] for k in range(3)], 1)
+    return out.astype(np.float32)
+
+
+def _is_faces(a) -> bool:
+    """a is an integer array or tensor of shape [F, 3] (the second entry of
+    a (verts, faces) mesh, as against a list of two points)."""
+    if torch.is_tensor(a):
+        return a.dim() == 2 and a.shape[1] == 3 and not (a.is_floating_point() or a.is_complex())
+    a = np.asarray(a)
+    return a.ndim == 2 and a.shape[1] == 3 and a.dtype.kind in "iu"
+
+
+def _as_cloud(x, samples, seed, device, transform, what):
+    """x (an [n, 3] array or tensor, a (verts, faces) mesh or a .ply path) as
+    a float32 device tensor [n, 3]: a mesh is sampled (nn.sample_mesh), its
+    vertices transformed first."""
+    from splatt3r_amd.nn import sample_mesh
+    faces = None
+    if isinstance(x, (str, pathlib.Path)):
+        verts, _, faces = read_mesh_ply(x)
+        if len(faces) == 0:
+            faces = None
+    elif isinstance(x, (tuple, list)) and len(x) == 2 and _is_faces(x[1]):
+        verts, faces = x
+    else:
+        verts = x
+    if transform is not None:
+        verts = apply_transform(verts, transform)
+    to_dev = lambda a, dt: (a if torch.is_tensor(a) else torch.from_numpy(
+        np.ascontiguousarray(a))).to(device=device, dtype=dt)
+    verts = to_dev(verts, torch.float32)
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError(f"eval_reconstruction: {what} must be [n, 3] points, a (verts, faces) "
+                         f"mesh or a .ply path, got shape {tuple(verts.shape)}")
+    if faces is None:
+        return verts.contiguous()
+    return sample_mesh(verts, to_dev(faces, torch.int32), samples, seed)[0]
+
+
+def eval_reconstruction(rec, gt, threshold=0.05, samples=200_000, transform=None, seed=0,
+                        max_dist=float("inf"), cell=None, device=None):
+    """Score reconstructed geometry against ground truth with exact nearest
+    neighbours on the device (splatt3r_amd.nn, include/s3k.h).  rec and gt
+    are each an [n, 3] array or tensor, a (verts, faces) mesh, of which
+    `samples` area-uniform points are drawn (seed: rec seed, gt seed + 1), or a
+    .ply path (read_mesh_ply; points when it has no faces).  transform =
+    (s, R, t) takes rec into gt's frame first (apply_transform: float64,
+    rounded once; the vertices of a mesh).  Returns
+      accuracy    mean distance from rec to the nearest gt point
+      completion  mean distance from gt to the nearest rec point
+      chamfer     (accuracy + completion) / 2
+      precision   share of rec within threshold of gt
+      recall      share of gt within threshold of rec (the completion ratio)
+      fscore      2 P R / (P + R), 0 when both are 0
+      n_rec, n_gt, threshold
+    The means are over the points that found a neighbour within max_dist (NaN
+    when none did); the shares are over all points.  threshold defaults to
+    5 cm, the usual indoor convention; nobody has tuned it here.  One host
+    read of ten numbers (and the sampler's check that a mesh has area)."""
+    from splatt3r_amd.nn import dist_stats, nearest
+    if device is None:
+        parts = [t for x in (rec, gt) for t in (x if isinstance(x, (tuple, list)) else (x,))]
+        device = next((t.device for t in parts if torch.is_tensor(t) and t.is_cuda),
+                      torch.device("cuda"))
+    threshold = float(threshold)
+    p_rec = _as_cloud(rec, samples, seed, device, transform, "rec")
+    p_gt = _as_cloud(gt, samples, seed + 1, device, None, "gt")
+    d_rec = nearest(p_rec, p_gt, max_dist, cell=cell)[1]
+    d_gt = nearest(p_gt, p_rec, max_dist, cell=cell)[1]
+    st = torch.stack([dist_stats(d_rec, threshold), dist_stats(d_gt, threshold)]).cpu().numpy()
+    n_rec, n_gt = p_rec.shape[0], p_gt.shape[0]
+    mean = lambda s: float(s[1] / s[0]) if s[0] > 0 else float("nan")
+    share = lambda s, n: float(s[3] / n) if n > 0 else float("nan")
+    acc, comp = mean(st[0]), mean(st[1])
+    P, R = share(st[0], n_rec), share(st[1], n_gt)
+    return dict(accuracy=acc, completion=comp, chamfer=0.5 * (acc + comp), precision=P, recall=R,
+                fscore=2.0 * P * R / (P + R) if P + R > 0 else 0.0, n_rec=n_rec, n_gt=n_gt,
+                threshold=threshold)
+
+
+def save_geometry_metrics(logdir, logfile, metrics):
+    """Write the dict eval_reconstruction / Frontend.eval_geometry returns as
+    one JSON line (arrays as nested lists)."""
+    import json
+
+    def plain(v):
+        if isinstance(v, dict):
+            return {k: plain(x) for k, x in v.items()}
+        if isinstance(v, np.ndarray):
+            return v.tolist()
+        if isinstance(v, np.generic):
+            return v.item()
+        return v
+    logdir = pathlib.Path(logdir)
+    logdir.mkdir(exist_ok=True, parents=True)
+    with open(logdir / logfile, "w") as f:
+        f.write(json.dumps(plain(metrics)) + "\n")
+
+
+def load_geometry_metrics(path):
+    """Reader for the files save_geometry_metrics writes: the dict, with the
+    trajectory's R and t as float64 arrays again."""
+    import json
+    with open(path) as f:
+        m = json.loads(f.readline())
+    tr = m.get("trajectory")
+    for d in (m, tr) if isinstance(tr, dict) else (m,):
+        for k in ("R", "t"):
+            if k in d:
+                d[k] = np.asarray(d[k], np.float64)
+    return m

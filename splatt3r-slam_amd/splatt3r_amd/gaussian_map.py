@@ -28,6 +28,7 @@ import torch
 from splatt3r_amd import _lib
 from splatt3r_amd import refine as _refine  # noqa: F401  (registers the s3d.h entry points)
 from splatt3r_amd import compact as _compact  # registers the s3v.h entry points
+from splatt3r_amd import nn as _nn  # noqa: F401  (registers the s3k.h entry points)
 
 
 class S3wMap(ctypes.Structure):

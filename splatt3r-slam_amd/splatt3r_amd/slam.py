@@ -532,6 +532,53 @@ class Frontend:
                  else self.K.detach().to("cpu", torch.float32).reshape(-1, 3, 3)[0])
             return save_mesh(path.parent, path.name, self.gmap, poses, K, h, w, voxel, **kw)
 
+    def eval_geometry(self, gt, voxel, traj_gt=None, timestamps=None, mesh_kw=None, **kw):
+        """Score the map's surface against ground-truth geometry `gt`
+        (evaluate.eval_reconstruction: points, a mesh or a .ply path) once
+        every queued render has been issued: the surface is the mesh save_mesh
+        writes (spacing `voxel`, mesh_kw to SharedGaussians.extract_mesh).
+        With traj_gt (a TUM-format path or (timestamps, poses)) the keyframe
+        poses, stamped timestamps[kf.frame_id] as save_traj stamps them, are
+        aligned to it (evaluate.eval_trajectory; with_scale, max_dt and align
+        are taken from **kw) and the surface is scored in the aligned frame;
+        the trajectory's dict is returned under "trajectory".  The rest of **kw
+        goes to eval_reconstruction.  Never called by the frame loop.  Returns
+        the metrics dict, or None when the session keeps no map (viz off), the
+        map is empty, there is no keyframe or the mesh has no triangle."""
+        from splatt3r_amd.evaluate import (as_SE3_data, eval_reconstruction, eval_trajectory,
+                                           keyframe_target)
+        from splatt3r_amd.splatt3r_utils import _estimate_default_intrinsics
+        self.drain()
+        if self.gmap is None or len(self.keyframes) == 0:
+            return None
+        self.sync_map()
+        # on the stream the map's appends were issued on
+        st = self.main_stream if self.main_stream is not None else \
+            torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(st):
+            dev = self.gmap.device
+            kfs = [self.keyframes[i] for i in range(len(self.keyframes))]
+            poses = torch.cat([_sim3_to_4x4(kf.T_WC).to(dev).reshape(1, 4, 4) for kf in kfs])
+            h, w = keyframe_target(kfs[0]).shape[-2:]
+            K = (_estimate_default_intrinsics(h, w, "cpu") if self.K is None
+                 else self.K.detach().to("cpu", torch.float32).reshape(-1, 3, 3)[0])
+            mesh = self.gmap.extract_mesh(poses, K, h, w, voxel, **(mesh_kw or {}))
+            if mesh is None or mesh[2].shape[0] == 0:
+                return None
+            traj = None
+            if traj_gt is not None:
+                if timestamps is None:
+                    raise ValueError("eval_geometry: traj_gt needs the frames' timestamps")
+                est = ([float(timestamps[kf.frame_id]) for kf in kfs],
+                       np.concatenate([as_SE3_data(kf.T_WC) for kf in kfs]))
+                tkw = {k: kw.pop(k) for k in ("with_scale", "max_dt", "align") if k in kw}
+                traj = eval_trajectory(est, traj_gt, **tkw)
+                kw.setdefault("transform", (traj["scale"], traj["R"], traj["t"]))
+            out = eval_reconstruction((mesh[0], mesh[2]), gt, **kw)
+            if traj is not None:
+                out["trajectory"] = traj
+            return out
+
     def close(self):
         """End the session: wait for queued renders, stop the render worker
         thread and release the decode-ahead slot this session left on the
