@@ -33,50 +33,10 @@ from typing import NamedTuple
 import torch
 import torch.nn as nn
 
-from splatt3r_amd import _lib
+from splatt3r_amd import _abi, _lib
 
 P_ = ctypes.c_void_p
-
-
-class _GsrSettings(ctypes.Structure):
-    _fields_ = [
-        ("image_height", ctypes.c_int),
-        ("image_width", ctypes.c_int),
-        ("tanfovx", ctypes.c_float),
-        ("tanfovy", ctypes.c_float),
-        ("scale_modifier", ctypes.c_float),
-        ("sh_degree", ctypes.c_int),
-        ("prefiltered", ctypes.c_int),
-        ("debug", ctypes.c_int),
-        ("bg", P_),
-        ("viewmatrix", P_),
-        ("projmatrix", P_),
-        ("campos", P_),
-    ]
-
-
-_SP = ctypes.POINTER(_GsrSettings)
-_lib.register({
-    "gsr_geom_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
-    "gsr_image_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
-    "gsr_binning_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
-    "gsr_preprocess": (ctypes.c_int, [_SP, ctypes.c_int64, ctypes.c_int] + [P_] * 7 +
-                       [P_, P_, ctypes.POINTER(ctypes.c_int64), P_]),
-    "gsr_render": (ctypes.c_int, [_SP, ctypes.c_int64, ctypes.c_int64, P_, P_, P_, P_, P_, P_]),
-    "gsr_backward": (ctypes.c_int, [_SP, ctypes.c_int64, ctypes.c_int, ctypes.c_int64] +
-                     [P_] * 8 + [P_, P_, P_, P_] + [P_] * 9 + [P_]),
-    "gsr_mark_visible": (ctypes.c_int, [ctypes.c_int64, P_, P_, P_, P_, P_]),
-    "gsr_forward_deferred": (ctypes.c_int, [_SP, ctypes.c_int64, ctypes.c_int] + [P_] * 7 +
-                             [P_, P_, P_, ctypes.c_int64, ctypes.c_int, P_, P_, P_, P_]),
-    "gsr_render_depth": (ctypes.c_int, [_SP, ctypes.c_int64, ctypes.c_int64] + [P_] * 10),
-    "gsr_forward_deferred_depth": (ctypes.c_int, [_SP, ctypes.c_int64, ctypes.c_int] + [P_] * 7 +
-                                   [P_, P_, P_, ctypes.c_int64, ctypes.c_int] + [P_] * 7),
-    "gsr_backward_depth": (ctypes.c_int, [_SP, ctypes.c_int64, ctypes.c_int, ctypes.c_int64] +
-                           [P_] * 8 + [P_, P_, P_, P_] + [P_] * 3 + [P_] * 9 + [P_, P_]),
-    "gsr_set_timing": (None, [ctypes.c_int]),
-    "gsr_set_binning": (None, [ctypes.c_int]),
-    "gsr_last_timing": (ctypes.c_int, [P_, ctypes.c_int]),
-})
+_GsrSettings = _abi.structs["gsr_settings"]     # include/gsr.h
 
 
 class GaussianRasterizationSettings(NamedTuple):

@@ -62,45 +62,6 @@ def refine_matches(D11, D21, p1, radius, dilation_max):
     return [_refine(D11, D21, p1, int(radius), int(dilation_max))]
 
 
-_lib.register({
-    "s3g_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int64,
-                                              ctypes.c_int]),
-    "s3g_ray_system": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-                                      ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                      ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
-                                      ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                      ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                      ctypes.c_void_p, ctypes.c_void_p]),
-    "s3g_calib_system": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-                                        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                        ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                        ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                        ctypes.c_float, ctypes.c_float, ctypes.c_int,
-                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                        ctypes.c_void_p]),
-    "s3g_gauss_newton_calib": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-                                              ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                              ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                              ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                              ctypes.c_float, ctypes.c_float, ctypes.c_int,
-                                              ctypes.c_float, ctypes.c_int, ctypes.c_void_p,
-                                              ctypes.c_void_p, ctypes.POINTER(ctypes.c_float),
-                                              ctypes.c_void_p]),
-    "s3g_gauss_newton_rays": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-                                             ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                             ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
-                                             ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                             ctypes.c_int, ctypes.c_float, ctypes.c_int,
-                                             ctypes.c_void_p, ctypes.c_void_p,
-                                             ctypes.POINTER(ctypes.c_float), ctypes.c_void_p]),
-})
-
 NUM_FIX = 1   # gn_kernels.cu:1156
 
 

@@ -1,4 +1,6 @@
 """ctypes binding of libsplatt3r_hip.so (the C ABI declared in include/*.h).
+Every signature is read from those headers (_abi.py) and bound when the
+library loads; no entry point is declared in Python.
 
 The product path always goes through this library; there is no Python or
 torch fallback for any kernel.  If the library is missing, `lib()` raises.
@@ -15,6 +17,8 @@ import threading
 
 import torch  # noqa: F401  (must be loaded before the HIP library, see above)
 
+from splatt3r_amd import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "_native", "libsplatt3r_hip.so")
 # S3_LIB_VARIANT=_pk: the library built with S3_PACKED_FP32=1 (packed-FP32
@@ -23,81 +27,12 @@ if os.environ.get("S3_LIB_VARIANT"):
     LIB_PATH = LIB_PATH.replace(".so", os.environ["S3_LIB_VARIANT"] + ".so")
 
 P = ctypes.c_void_p
-I32 = ctypes.c_int
-I64 = ctypes.c_int64
-F32 = ctypes.c_float
-SZ = ctypes.c_size_t
 
-# name -> (restype, argtypes).  Kept in the order of include/*.h.
-SIGNATURES: dict[str, tuple] = {
-    # s3_common.h
-    "s3_last_error": (ctypes.c_char_p, []),
-    "s3_abi_version": (I32, []),
-    "s3_arch": (ctypes.c_char_p, []),
-    "s3_stream_create": (I32, [I32, I32, ctypes.POINTER(P)]),
-    "s3_stream_destroy": (I32, [P]),
-    # s3lie.h
-    "s3lie_sim3_mul": (I32, [P, I64, P, I64, P, I64, P]),
-    "s3lie_sim3_inv": (I32, [P, P, I64, P]),
-    "s3lie_sim3_act": (I32, [P, I64, P, P, I64, P]),
-    "s3lie_sim3_exp": (I32, [P, P, I64, P]),
-    "s3lie_sim3_log": (I32, [P, P, I64, P]),
-    "s3lie_sim3_retr": (I32, [P, I64, P, I64, P, I64, P]),
-    "s3lie_sim3_matrix": (I32, [P, P, I64, P]),
-    "s3lie_se3_matrix": (I32, [P, P, I64, P]),
-    "s3lie_pose_retr": (I32, [P, P, I64, I64, P]),
-    "s3lie_sim3_retr_host": (None, [P, P, P]),
-    "s3lie_sim3_mul_host": (None, [P, P, P]),
-    "s3lie_sim3_inv_host": (None, [P, P]),
-    # s3m.h
-    "s3m_iter_proj": (I32, [P, P, P, P, P, I32, I32, I32, I32, I32, F32, F32, P]),
-    "s3m_refine_matches": (I32, [P, P, P, P, I32, I32, I32, I32, I32, I32, I32, P]),
-    "s3m_refine_set_lanes": (None, [I32]),
-    "s3m_refine_set_prefetch": (None, [I32]),
-    "s3m_refine_set_sort": (None, [I32]),
-    "s3m_prep_iter_proj": (I32, [P, P, P, P, P, P, I32, I32, I32, P]),
-    "s3m_occlusion": (I32, [P, P, P, P, P, P, I32, I32, I32, F32, P]),
-    "s3m_pixel_to_lin": (I32, [P, P, I64, I32, P]),
-    # s3p.h
-    "s3p_workspace_bytes": (SZ, [I32, I32, I32, I32]),
-    "s3p_derivs_bytes": (SZ, [I32, I32, I32, I32]),
-    "s3p_forward": (I32, [P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P]),
-    "s3p_backward": (I32, [P, P, P, P, P, P, I32, I32, I32, I32, P, P]),
-    "s3p_window": (None, [P]),
-    # s3c.h
-    "s3c_loss_mask_workspace_bytes": (SZ, [I32, I32, I32]),
-    "s3c_loss_mask": (I32, [P, P, P, P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P]),
-    # s3w.h (splat rows; the map's other entries are registered by their modules)
-    "s3w_map_to_splats": (I32, [P, P, P, P, P, I64, F32, P, P]),
-    "s3w_map_from_splats": (I32, [P, P, I64, ctypes.c_int32, P]),
-    # s3o.h (hp: POINTER(refine.S3oAdam), passed with ctypes.byref)
-    "s3o_activate": (I32, [P, I64, F32, P, P, P, P, P, P]),
-    "s3o_adam_step": (I32, [P, P, P, I64, P, P, P, P, P, P, P, P, P]),
-    # s3a.h (map: POINTER(gaussian_map.S3wMap), passed with ctypes.byref)
-    "s3a_reanchor_workspace_bytes": (SZ, [ctypes.c_int32]),
-    "s3a_map_reanchor": (I32, [P, P, P, ctypes.c_int32, P, P, P, SZ, P]),
-    "s3a_set_path": (None, [I32]),
-    # s3f.h
-    "s3f_integrate_workspace_bytes": (SZ, [ctypes.c_int32]),
-    "s3f_integrate": (I32, [P, P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, F32, F32, F32,
-                            F32, F32, F32, P, P, P, P, P, ctypes.c_int32, ctypes.c_int32,
-                            ctypes.c_int32, P, SZ, P]),
-    "s3f_mesh_workspace_bytes": (SZ, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
-    "s3f_mesh_count": (I32, [P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, F32, P, P, SZ,
-                             P]),
-    "s3f_mesh_emit": (I32, [P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, F32, F32, F32,
-                            F32, I64, I64, P, P, P, I64, I64, P, SZ, P]),
-}
+# name -> (restype, argtypes) of every entry point include/*.h declares
+SIGNATURES: dict[str, tuple] = _abi.functions
 
 _lock = threading.Lock()
 _lib = None
-
-
-def register(sigs: dict) -> None:
-    """Add signatures (used by modules that own a header)."""
-    SIGNATURES.update(sigs)
-    if _lib is not None:
-        _bind(_lib, sigs)
 
 
 def _bind(l, sigs):

@@ -18,28 +18,10 @@ import math
 
 import torch
 
-from splatt3r_amd import _lib
+from splatt3r_amd import _abi, _lib
 
-
-class S3vIn(ctypes.Structure):
-    """s3v_in of include/s3v.h."""
-    _fields_ = [(k, ctypes.c_void_p) for k in ("means", "cov_triu", "colors", "opacities",
-                                               "kf_id")]
-
-
-class S3vOut(ctypes.Structure):
-    """s3v_out of include/s3v.h."""
-    _fields_ = S3vIn._fields_
-
-
-_P = ctypes.c_void_p
-_lib.register({
-    # s3v.h (in, out: POINTER(S3vIn), POINTER(S3vOut), passed with ctypes.byref;
-    # origin: a host double[3])
-    "s3v_merge_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
-    "s3v_merge": (ctypes.c_int, [_P, _P, ctypes.c_int64, _P, ctypes.c_double, _P, _P, _P, _P, _P,
-                                 _P, ctypes.c_size_t, _P]),
-})
+S3vIn = _abi.structs["s3v_in"]      # include/s3v.h
+S3vOut = _abi.structs["s3v_out"]
 
 
 def check_grid(voxel, origin, fn: str):

@@ -25,26 +25,10 @@ from typing import Optional
 import numpy as np
 import torch
 
-from splatt3r_amd import _lib
-from splatt3r_amd import refine as _refine  # noqa: F401  (registers the s3d.h entry points)
-from splatt3r_amd import compact as _compact  # registers the s3v.h entry points
-from splatt3r_amd import nn as _nn  # noqa: F401  (registers the s3k.h entry points)
+from splatt3r_amd import _abi, _lib
+from splatt3r_amd import compact as _compact
 
-
-class S3wMap(ctypes.Structure):
-    _fields_ = [("means", ctypes.c_void_p), ("cov_triu", ctypes.c_void_p),
-                ("colors", ctypes.c_void_p), ("opacities", ctypes.c_void_p),
-                ("kf_id", ctypes.c_void_p), ("n", ctypes.c_void_p), ("cap", ctypes.c_int64)]
-
-
-_P = ctypes.c_void_p
-_lib.register({
-    "s3w_map_append_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
-    "s3w_map_append": (ctypes.c_int, [ctypes.POINTER(S3wMap), _P, _P, ctypes.c_int64,
-                                      ctypes.c_float, ctypes.c_int32, _P, _P]),
-    "s3w_map_scale": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, ctypes.c_float, ctypes.c_float,
-                                     _P, _P, _P]),
-})
+S3wMap = _abi.structs["s3w_map"]    # include/s3w.h
 
 # the viz clear colour (visualization.py:523-525)
 VIZ_BG = (0.118, 0.137, 0.149)

@@ -15,7 +15,6 @@ Importing this module does not initialise the GPU.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 import threading
 import warnings
@@ -24,21 +23,10 @@ import numpy as np
 import torch
 
 from splatt3r_amd import _lib
-from splatt3r_amd import intrinsics as _intrinsics  # noqa: F401  (registers the s3u_* signatures)
 
 LANCZOS = "lanczos"
 BICUBIC = "bicubic"
 PRECISION_BITS = 22            # Pillow: 32 - 8 - 2
-
-_P, _I = ctypes.c_void_p, ctypes.c_int
-_lib.register({
-    "s3i_ingest": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I,
-                        _P, _P, _P, _P, _P]),
-    "s3i_workspace_bytes": (ctypes.c_size_t, [_I, _I, _I]),
-    "s3i_fused_fits": (_I, [_I, _I, _I, _I, _I, _I]),
-    "s3i_set_path": (None, [_I]),
-})
-
 
 # --------------------------------------------------------------- geometry --
 def ingest_geometry(in_h: int, in_w: int, size: int, square_ok: bool = False):

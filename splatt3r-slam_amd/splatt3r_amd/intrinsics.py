@@ -23,7 +23,6 @@ Importing this module does not initialise the GPU.
 """
 from __future__ import annotations
 
-import ctypes
 import threading
 import warnings
 
@@ -32,11 +31,6 @@ import torch
 
 from splatt3r_amd import _lib
 from splatt3r_amd.config import config
-
-_P, _I = ctypes.c_void_p, ctypes.c_int
-_lib.register({
-    "s3u_remap": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
-})
 
 INTER_BITS = 5                      # cv2: maps are quantised to 1/32 pixel
 INTER_TAB_SIZE = 1 << INTER_BITS

@@ -20,9 +20,10 @@ from __future__ import annotations
 
 import torch
 
-from splatt3r_amd import _lib
+from splatt3r_amd import _abi, _lib
 
-COND_FRUSTUM, COND_DEPTH, COND_MATCH = 1, 2, 4
+COND_FRUSTUM, COND_DEPTH, COND_MATCH = (
+    _abi.constants[k] for k in ("S3C_COND_FRUSTUM", "S3C_COND_DEPTH", "S3C_COND_MATCH"))
 
 
 def _check(depth_1, intrinsics_1, c2w_1, depth_2, intrinsics_2, c2w_2, fn):

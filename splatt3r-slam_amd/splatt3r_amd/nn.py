@@ -21,29 +21,9 @@ import math
 
 import torch
 
-from splatt3r_amd import _lib
+from splatt3r_amd import _abi, _lib
 
-_P = ctypes.c_void_p
-_I32 = ctypes.c_int32
-_I64 = ctypes.c_int64
-_F64 = ctypes.c_double
-_SZ = ctypes.c_size_t
-_lib.register({
-    # s3k.h (origin: a host double[3])
-    "s3k_grid_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32]),
-    "s3k_grid_build": (ctypes.c_int, [_P, _I64, _P, _F64, _I32, _I32, _I32, _P, _SZ, _P, _P]),
-    "s3k_query_workspace_bytes": (_SZ, [_I64]),
-    "s3k_query": (ctypes.c_int, [_P, _SZ, _I64, _P, _F64, _I32, _I32, _I32, _P, _I64, _F64, _P, _P,
-                                 _P, _SZ, _P]),
-    "s3k_set_query_mode": (None, [_I32]),
-    "s3k_dist_stats_workspace_bytes": (_SZ, [_I64]),
-    "s3k_dist_stats": (ctypes.c_int, [_P, _I64, _F64, _P, _P, _SZ, _P]),
-    "s3k_sample_workspace_bytes": (_SZ, [_I64]),
-    "s3k_sample_mesh": (ctypes.c_int, [_P, _I64, _P, _I64, _I64, ctypes.c_uint64, _P, _P, _P, _P,
-                                       _P, _SZ, _P]),
-})
-
-MAX_CELLS = 1 << 27          # S3K_MAX_CELLS
+MAX_CELLS = _abi.constants["S3K_MAX_CELLS"]
 
 
 def _points(t, name: str, fn: str) -> torch.Tensor:

@@ -16,80 +16,17 @@ from typing import Sequence
 
 import torch
 
-from splatt3r_amd import _lib
+from splatt3r_amd import _abi, _lib
 
 P = ctypes.c_void_p
-G = 4  # S3N_MAX_GROUPS
-I64 = ctypes.c_int64
-
-
-class GemmArgs(ctypes.Structure):
-    _fields_ = [
-        ("M", ctypes.c_int), ("N", ctypes.c_int), ("K", ctypes.c_int), ("groups", ctypes.c_int),
-        ("A", P * G), ("lda", I64),
-        ("B", P * G), ("ldb", I64),
-        ("bias", P * G),
-        ("R1", P * G), ("ldr1", I64), ("r1_f16", ctypes.c_int),
-        ("R2", P * G), ("ldr2", I64), ("r2_f16", ctypes.c_int),
-        ("C", P * G), ("ldc", I64), ("c_f16", ctypes.c_int),
-        ("C2", P * G), ("ldc2", I64),
-        ("act", ctypes.c_int), ("store_mode", ctypes.c_int), ("a_mode", ctypes.c_int),
-        ("cH", ctypes.c_int), ("cW", ctypes.c_int), ("cC", ctypes.c_int), ("ksize", ctypes.c_int),
-        ("stride", ctypes.c_int), ("pad", ctypes.c_int), ("oH", ctypes.c_int), ("oW", ctypes.c_int),
-        ("relu_in", ctypes.c_int),
-        ("sH", ctypes.c_int), ("sW", ctypes.c_int), ("sS", ctypes.c_int), ("sCout", ctypes.c_int),
-        ("split_k", ctypes.c_int), ("tile", ctypes.c_int), ("workspace", P),
-        ("rope_cos", P), ("rope_sin", P), ("rope_maxpos", ctypes.c_int),
-        ("rope_ncols", ctypes.c_int), ("rope_pos", P * G),
-        ("tail_w", P * G), ("tail_b", P * G), ("tail_out", P * G), ("tail_n", ctypes.c_int),
-        ("ld_tail", I64),
-        ("Bp", P * G),
-    ]
-
-
-class AttnArgs(ctypes.Structure):
-    _fields_ = [
-        ("B", ctypes.c_int), ("Nq", ctypes.c_int), ("Nk", ctypes.c_int), ("H", ctypes.c_int),
-        ("groups", ctypes.c_int),
-        ("Q", P * G), ("K", P * G), ("V", P * G),
-        ("q_stride", I64), ("k_stride", I64), ("v_stride", I64),
-        ("qpos", P * G), ("kpos", P * G),
-        ("rope_cos", P), ("rope_sin", P), ("rope_maxpos", ctypes.c_int),
-        ("O", P * G), ("o_stride", I64),
-        ("scale", ctypes.c_float),
-    ]
-
-
-class GemmTile(ctypes.Structure):
-    """s3n_gemm_tile (include/s3n.h): one line of csrc/net_gemm_tiles.def."""
-    _fields_ = [(f, ctypes.c_int) for f in ("id", "bm", "bn", "bk", "kg", "mf", "regs_epilogue",
-                                            "halo", "bdirect", "tail_ok", "tuner")]
-
-
-_GP = ctypes.POINTER(GemmArgs)
-_AP = ctypes.POINTER(AttnArgs)
 _PP = ctypes.POINTER(P)
-_lib.register({
-    "s3n_gemm": (ctypes.c_int, [_GP, P]),
-    "s3n_gemm_workspace_bytes": (ctypes.c_size_t, [_GP]),
-    "s3n_gemm_tile_count": (ctypes.c_int, []),
-    "s3n_gemm_tile_info": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(GemmTile)]),
-    "s3n_gemm_set_debug": (None, [ctypes.c_int]),
-    "s3n_gemm_set_xcd_flags": (None, [ctypes.c_int]),
-    "s3n_attention_set_variant": (None, [ctypes.c_int]),
-    "s3n_attention": (ctypes.c_int, [_AP, P]),
-    "s3n_layernorm": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _PP, I64, _PP, _PP,
-                                     ctypes.c_float, _PP, I64, _PP, I64, P]),
-    "s3n_patch_im2col": (ctypes.c_int, [P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                        P, P]),
-    "s3n_upsample2x": (ctypes.c_int, [ctypes.c_int, _PP, _PP, ctypes.c_int, ctypes.c_int,
-                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P]),
-    "s3n_gaussian_postprocess": (ctypes.c_int, [I64, P, ctypes.c_int, P, P, ctypes.c_int,
-                                                ctypes.c_int] + [P] * 10 + [P]),
-    "s3n_prng_fill": (ctypes.c_int, [P, I64, ctypes.c_uint64, ctypes.c_float, ctypes.c_float, P]),
-    "s3n_cast_f16": (ctypes.c_int, [P, I64, P, I64, I64, ctypes.c_int, P]),
-    "s3n_f16_saturations": (ctypes.c_int, [ctypes.c_int]),
-})
+_C = _abi.constants
+G = _C["S3N_MAX_GROUPS"]
+
+# the argument structs of include/s3n.h
+GemmArgs = _abi.structs["s3n_gemm_args"]
+AttnArgs = _abi.structs["s3n_attn_args"]
+GemmTile = _abi.structs["s3n_gemm_tile"]      # one line of csrc/net_gemm_tiles.def
 
 
 def f16_saturations(reset: bool = False) -> int:
@@ -102,7 +39,7 @@ def f16_saturations(reset: bool = False) -> int:
         raise RuntimeError("s3n_f16_saturations: HIP error")
     return n
 
-ACT = {"none": 0, "gelu": 1, "relu": 2}
+ACT = {"none": _C["S3N_ACT_NONE"], "gelu": _C["S3N_ACT_GELU"], "relu": _C["S3N_ACT_RELU"]}
 
 # S3_SYNC_DEBUG=1: run plans op by op with a device sync after each (fault
 # localisation); S3_GRAPHS=0 disables HIP-graph capture.
@@ -403,10 +340,11 @@ def _tune_candidates(a, split_ok, like=None):
             continue
         if a.tail_n and (bn != a.N or tile not in t.tail_ok):
             continue
-        if tile in t.halo and not (a.a_mode == 1 and a.ksize == 3 and a.stride == 1 and
-                                  a.oW % bm == 0 and a.cC % 64 == 0):
+        if tile in t.halo and not (a.a_mode == _C["S3N_A_CONV"] and a.ksize == 3 and
+                                  a.stride == 1 and a.oW % bm == 0 and a.cC % 64 == 0):
             continue
-        if tile in t.bdirect and not (a.Bp[0] and a.a_mode == 0 and not a.tail_n and a.K % 32 == 0):
+        if tile in t.bdirect and not (a.Bp[0] and a.a_mode == _C["S3N_A_DENSE"] and not a.tail_n and
+                                      a.K % 32 == 0):
             continue
         tiles = a.groups * -(-a.M // bm) * -(-a.N // bn)
         for sk in (1, 2, 3, 4, 6, 8):
@@ -440,11 +378,11 @@ def _tuned(a, A, B, bias, rope, rope_pos, split_ok, like=None):
             t.normal_(0.0, 0.1, generator=gen)
         return t
 
-    if a.a_mode == 0:
+    if a.a_mode == _C["S3N_A_DENSE"]:
         a_elems = (a.M - 1) * a.lda + a.K
     else:
         a_elems = a.M // (a.oH * a.oW) * a.cH * a.cW * a.cC
-    if a.store_mode == 0:
+    if a.store_mode == _C["S3N_STORE_PLAIN"]:
         c_elems = (a.M - 1) * a.ldc + a.N
     else:
         c_elems = a.M * a.sS * a.sS * a.sCout
@@ -617,14 +555,14 @@ def gemm(A, B, C, M, N, K, *, lda, ldb=None, ldc=None, bias=None, act="none", R1
         a.C2 = _parr(C2)
         a.ldc2 = int(ldc2)
     if conv is not None:
-        a.a_mode = 1
+        a.a_mode = _C["S3N_A_CONV"]
         a.cH, a.cW, a.cC = conv["H"], conv["W"], conv["C"]
         a.ksize, a.stride, a.pad = conv["k"], conv["stride"], conv["pad"]
         a.oH, a.oW = conv["oH"], conv["oW"]
         a.relu_in = int(conv.get("relu_in", False))
     if store is not None:
         mode, sH, sW, s, cout = store
-        a.store_mode = {"convt": 1, "pixshuf": 2}[mode]
+        a.store_mode = {"convt": _C["S3N_STORE_CONVT"], "pixshuf": _C["S3N_STORE_PIXSHUF"]}[mode]
         a.sH, a.sW, a.sS, a.sCout = sH, sW, s, cout
     if rope_pos is not None:   # fused RoPE2D epilogue on the first rope_ncols columns
         a.rope_cos, a.rope_sin = rope[0].data_ptr(), rope[1].data_ptr()

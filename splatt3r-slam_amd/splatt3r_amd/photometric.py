@@ -26,9 +26,11 @@ from __future__ import annotations
 import torch
 from torch.autograd.function import once_differentiable
 
-from splatt3r_amd import _lib
+from splatt3r_amd import _abi, _lib
 
-SUM_SQ, SUM_ABS, SUM_MS, SUM_M, SUM_CROP, NSUMS = 0, 1, 2, 3, 4, 5
+SUM_SQ, SUM_ABS, SUM_MS, SUM_M, SUM_CROP, NSUMS = (
+    _abi.constants[k] for k in ("S3P_SUM_SQ", "S3P_SUM_ABS", "S3P_SUM_MS", "S3P_SUM_M",
+                                "S3P_SUM_CROP", "S3P_NSUMS"))
 WIN = 11
 RADIUS = 5
 

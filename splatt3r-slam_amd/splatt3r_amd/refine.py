@@ -31,47 +31,14 @@ from typing import Optional, Sequence
 
 import torch
 
-from splatt3r_amd import _lib
+from splatt3r_amd import _abi, _lib
 
 GROUPS = ("means", "f_dc", "opacity", "scale", "rotation")
 
 
-class S3oAdam(ctypes.Structure):
-    """s3o_adam of include/s3o.h."""
-    _fields_ = [("lr", ctypes.c_float * 5), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float),
-                ("eps", ctypes.c_float), ("bias1", ctypes.c_float),
-                ("bias2_sqrt", ctypes.c_float), ("render_scale", ctypes.c_float)]
-
-
-class S3dParams(ctypes.Structure):
-    """s3d_params of include/s3d.h."""
-    _fields_ = [("grad_threshold", ctypes.c_float), ("split_scale", ctypes.c_float),
-                ("min_opacity", ctypes.c_float), ("max_scale", ctypes.c_float),
-                ("max_screen_radius", ctypes.c_int32), ("seed", ctypes.c_uint64),
-                ("pass_", ctypes.c_uint32)]
-
-
-class S3xPoseAdam(ctypes.Structure):
-    """s3x_pose_adam of include/s3x.h."""
-    _fields_ = [(k, ctypes.c_double) for k in ("lr_translation", "lr_rotation", "beta1", "beta2",
-                                               "eps", "bias1", "bias2_sqrt", "render_scale")]
-
-
-_P = ctypes.c_void_p
-_lib.register({
-    # s3x.h (hp: POINTER(S3xPoseAdam), passed with ctypes.byref)
-    "s3x_pose_grad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
-    "s3x_pose_grad": (ctypes.c_int, [_P] * 8 + [ctypes.c_int64, _P, _P, _P, ctypes.c_size_t, _P]),
-    "s3x_pose_step": (ctypes.c_int, [_P] * 10),
-})
-_lib.register({
-    # s3d.h (params: POINTER(S3dParams), passed with ctypes.byref)
-    "s3d_accumulate": (ctypes.c_int, [_P, _P, ctypes.c_int64, _P, _P, _P, _P]),
-    "s3d_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
-    "s3d_densify": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, _P, _P, _P, _P, ctypes.c_int64,
-                                   _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
-    "s3d_reset_opacity": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, ctypes.c_float, _P]),
-})
+S3oAdam = _abi.structs["s3o_adam"]              # include/s3o.h
+S3dParams = _abi.structs["s3d_params"]          # include/s3d.h
+S3xPoseAdam = _abi.structs["s3x_pose_adam"]     # include/s3x.h
 
 COUNTS = ("pruned", "cloned", "split", "denied")
 

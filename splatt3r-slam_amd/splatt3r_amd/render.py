@@ -13,19 +13,12 @@ rasterizer directly.
 """
 from __future__ import annotations
 
-import ctypes
 from math import isqrt
 
 import torch
 
 from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
 from splatt3r_amd import _lib
-
-_lib.register({
-    "s3r_camera": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_float] + [ctypes.c_void_p] * 4),
-    "s3r_pack_splats": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int64, ctypes.c_int,
-                        ctypes.c_float, ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_void_p]),
-})
 
 
 def normalize_intrinsics(intrinsics, image_shape):

@@ -21,32 +21,12 @@ scores per query (the reference's torch.topk on the CPU).
 """
 from __future__ import annotations
 
-import ctypes
 import dataclasses
 from typing import Optional, Tuple
 
 import torch
 
 from splatt3r_amd import _lib
-
-_lib.register({
-    "s3q_whiten": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_void_p]),
-    "s3q_linear": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
-    "s3q_select_local": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] * 4 +
-                         [ctypes.c_void_p] * 4),
-    "s3q_row_sqnorm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                      ctypes.c_void_p, ctypes.c_void_p]),
-    "s3q_l2_topk_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
-    "s3q_l2_topk": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 +
-                    [ctypes.c_void_p] * 4),
-    "s3q_asmk_aggregate_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
-    "s3q_asmk_aggregate": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 +
-                           [ctypes.c_void_p] * 5),
-    "s3q_asmk_search": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] +
-                        [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                                                 ctypes.c_float, ctypes.c_void_p, ctypes.c_int,
-                                                 ctypes.c_void_p, ctypes.c_void_p]),
-})
 
 # asmk_params of Retriever (processor.py:84-89)
 ASMK_PARAMS = {"build_ivf": {"kernel": {"binary": True}, "ivf": {"use_idf": False},

@@ -22,8 +22,7 @@ import numpy as np
 import torch
 
 import lietorch
-from splatt3r_amd import _lib, matching
-from splatt3r_amd import ingest  # noqa: F401  (registers the s3i_* signatures)
+from splatt3r_amd import _abi, _lib, matching
 from splatt3r_amd.config import config
 from splatt3r_amd.render import (DecoderSplattingCUDA, camera_settings, camera_settings_sim3,
                                   normalize_intrinsics,
@@ -491,22 +490,8 @@ def splatt3r_render(model, frame, ref_frame, K=None, target_T_WC=None, sizing=No
     return out
 
 
-class S3wView(ctypes.Structure):
-    _fields_ = [("means", ctypes.c_void_p), ("scales", ctypes.c_void_p),
-                ("rotations", ctypes.c_void_p), ("sh", ctypes.c_void_p),
-                ("opacities", ctypes.c_void_p), ("conf", ctypes.c_void_p),
-                ("img", ctypes.c_void_p), ("H", ctypes.c_int), ("W", ctypes.c_int),
-                ("d_sh", ctypes.c_int), ("stride", ctypes.c_int)]
+S3wView = _abi.structs["s3w_view"]      # include/s3w.h
 
-
-_P = ctypes.c_void_p
-_lib.register({
-    "s3w_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
-    "s3w_set_path": (None, [ctypes.c_int]),
-    "s3w_gaussians_to_world": (ctypes.c_int, [ctypes.POINTER(S3wView), _P, ctypes.c_float,
-                                              ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                              _P, _P, _P, _P]),
-})
 _WS: dict = {}
 
 

@@ -23,27 +23,6 @@ import lietorch
 from splatt3r_amd import _lib
 from splatt3r_amd.config import config
 
-P_ = ctypes.c_void_p
-_lib.register({
-    "s3t_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
-    "s3t_ray_dist_normal_eqs": (ctypes.c_int, [P_, P_, P_, P_, P_, ctypes.c_int64, ctypes.c_float,
-                                               ctypes.c_float, ctypes.c_float, P_, P_, P_]),
-    "s3t_gn_iterations": (ctypes.c_int, [P_, P_, P_, P_, ctypes.c_int64, ctypes.c_float,
-                                         ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int,
-                                         ctypes.c_float, ctypes.c_float, P_, P_, P_, P_, P_]),
-    "s3t_calib_normal_eqs": (ctypes.c_int, [P_, P_, P_, P_, P_, ctypes.c_int64, P_, ctypes.c_int,
-                                            ctypes.c_int, ctypes.c_float, ctypes.c_float,
-                                            ctypes.c_float, ctypes.c_float, ctypes.c_float, P_, P_,
-                                            P_]),
-    "s3t_gn_iterations_calib": (ctypes.c_int, [P_, P_, P_, P_, ctypes.c_int64, P_, ctypes.c_int,
-                                               ctypes.c_int, ctypes.c_float, ctypes.c_float,
-                                               ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                               ctypes.c_int, ctypes.c_int, ctypes.c_float,
-                                               ctypes.c_float, P_, P_, P_, P_, P_]),
-    "s3t_track_prep": (ctypes.c_int, [P_, P_, P_, P_, P_, P_, P_, ctypes.c_int64, ctypes.c_float,
-                                      ctypes.c_float, P_, P_, P_, P_, P_, P_]),
-})
-
 
 def track_prep(idx, vm, Xf, Cf, Ck, Qff, Qkf, C_conf, Q_conf):
     """tracker.py:28-91's correspondence filter in one HIP pass

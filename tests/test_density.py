@@ -409,7 +409,7 @@ def test_python_validation_needs_no_gpu():
     dc.begin(10, T, "cpu")
     hp = dc.params(2)
     assert abs(hp.split_scale - 0.011) < 1e-8 and abs(hp.max_scale - 0.11) < 1e-7
-    assert hp.pass_ == 2 and dc.origin.tolist() == list(range(10))
+    assert getattr(hp, "pass") == 2 and dc.origin.tolist() == list(range(10))
     with pytest.raises(ValueError, match="capacity"):
         refine.DensityControl(capacity=5).begin(10, T, "cpu")
     # origin composition: pass 1 keeps 0, clones 1, splits 2; pass 2 splits the copy of 1
@@ -633,8 +633,9 @@ def test_hip_loop_with_density_control(parity):
     for k, inp, hp, cap, out, counts in passes:
         p = dict(grad_threshold=hp.grad_threshold, split_scale=hp.split_scale,
                  min_opacity=hp.min_opacity, max_scale=hp.max_scale,
-                 max_screen_radius=hp.max_screen_radius, seed=hp.seed, **{"pass": hp.pass_})
-        assert hp.pass_ == k
+                 max_screen_radius=hp.max_screen_radius, seed=hp.seed,
+                 **{"pass": getattr(hp, "pass")})
+        assert getattr(hp, "pass") == k
         want = D.densify(inp[0], inp[1], inp[2], tuple(inp[3:6]), p, cap)
         assert want["near"].mean() <= 0.01
         got = dict(rows=out[0], m=out[1], v=out[2], origin=out[3], n_out=len(out[0]),
