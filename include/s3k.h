@@ -45,6 +45,28 @@
  * (one radix sort of the cell ids, csrc/radix_pass.hpp) and written back to
  * their own positions; one thread per query.
  *
+ * k nearest (s3k_knn).  q [m, 3] float32, 1 <= k <= 32 -> idx [m, k] int32,
+ * dist [m, k] float32, mean_d [m], mean_d2 [m] float32; each output may be
+ * null, not all four.  The candidates of query j are the kept rows i, without
+ * row i = j when exclude_self is set (by index alone: the caller's promise
+ * that q is ref, so m <= n); d2_i as above, and a candidate counts only if
+ * d2 <= max_dist max_dist.  The row holds the first min(k, candidates)
+ * candidates in ascending (d2, i) order, a total order: slot s has the index
+ * i_s and dist = (float)sqrt(d2_s); an unfilled slot has -1 and +inf, and a
+ * non-finite query row fills none.  With c filled slots, summed in slot
+ * order in double,
+ *   mean_d  = (float)((sum_s sqrt(d2_s)) / c)   (the double root, not dist)
+ *   mean_d2 = (float)((sum_s d2_s) / c)
+ * and +inf for both when c = 0.  The result is bit for bit that of sorting
+ * every row, whatever the grid.  The walk is the query's, with the stop rule
+ * on slot k - 1: after ring r it stops when k slots are filled and
+ *   d2_{k-1} < (r cell (1 - 2^-20))^2,
+ * strict, so a row that ties with the k-th is never given up; the other two
+ * stops and the linear rest are unchanged, and a query visits no cell and no
+ * row twice.  One thread per query in cell order; the k slots live in
+ * registers (4, 8, 16 or 32 of them, the fewest that hold k).
+ * s3k_set_query_mode does not apply.
+ *
  * Statistics (s3k_dist_stats).  Over the finite entries of dist [m]:
  *   out[0] their count, out[1] sum d, out[2] sum d d, out[3] the count of
  *   d <= threshold, out[4] the maximum (-inf when there is none)
@@ -82,6 +104,7 @@
 #include "s3_common.h"
 
 #define S3K_MAX_CELLS (1 << 27)
+#define S3K_MAX_K 32
 
 #ifdef __cplusplus
 extern "C" {
@@ -110,6 +133,20 @@ size_t s3k_query_workspace_bytes(int64_t m);
 int s3k_query(const void* grid, size_t grid_bytes, int64_t n, const double* origin, double cell,
               int32_t nx, int32_t ny, int32_t nz, const float* q, int64_t m, double max_dist,
               int32_t* idx, float* dist, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Bytes of the workspace of s3k_knn over m rows (0 for m <= 0 or
+ * m > 2^31 - 2048): the sort's columns and histograms. */
+size_t s3k_knn_workspace_bytes(int64_t m);
+
+/* The k nearest rows of the grid (built with the same n, origin, cell, dims)
+ * for each of q [m, 3] (device), 1 <= k <= S3K_MAX_K: idx [m, k] int32,
+ * dist [m, k], mean_d [m], mean_d2 [m] float32 (device; each may be null,
+ * not all).  exclude_self != 0: row j is no candidate of query j (m <= n).
+ * m = 0 does nothing. */
+int s3k_knn(const void* grid, size_t grid_bytes, int64_t n, const double* origin, double cell,
+            int32_t nx, int32_t ny, int32_t nz, const float* q, int64_t m, int32_t k,
+            int32_t exclude_self, double max_dist, int32_t* idx, float* dist, float* mean_d,
+            float* mean_d2, void* workspace, size_t workspace_bytes, void* stream);
 
 /* How s3k_query walks (process-wide; for measurements, every mode returns
  * the same bits): 0 queries sorted by cell, one thread each (the default);

@@ -17,6 +17,11 @@
 //           k_nn_query_wave  the same with one wave per query, and k_nn_query
 //                            without the sort: s3k_set_query_mode, measured and
 //                            not chosen, kept for the benchmark
+//   knn     k_nn_qkeys, sort  as the query
+//           k_nn_knn<CAP>    one thread per query in cell order: s3k::search_k
+//                            with CAP = 4, 8, 16 or 32 register slots (the
+//                            smallest that holds k), the k slots and the two
+//                            row means written to the query's own row
 //   stats   k_nn_stats_part, k_nn_stats_final      fixed-order double sums
 //   sample  k_nn_area        face areas, bad faces, A_max (atomicMax on the
 //                            bits of a non-negative double: an integer atomic)
@@ -207,6 +212,24 @@ k_nn_query_wave(s3k::Grid g, const float* __restrict__ q, const uint32_t* __rest
     idx[i] = h.i;
     dist[i] = (float)sqrt(h.d2);
   }
+}
+
+// k nearest rows of each query: any of the four outputs may be null
+template <int CAP>
+__global__ void __launch_bounds__(kT)
+k_nn_knn(s3k::Grid g, const float* __restrict__ q, const uint32_t* __restrict__ order, int64_t m,
+         int32_t k, int32_t exclude_self, double max_dist, int32_t* __restrict__ idx,
+         float* __restrict__ dist, float* __restrict__ mean_d, float* __restrict__ mean_d2) {
+  const int64_t j = (int64_t)blockIdx.x * kT + threadIdx.x;
+  if (j >= m) return;
+  const int64_t i = order[j];
+  s3k::HitK<CAP> h;
+  s3k::search_k(g, q[3 * i], q[3 * i + 1], q[3 * i + 2], k, exclude_self ? (int32_t)i : -1,
+                max_dist, h, nullptr);
+  const s3k::RowStats o = s3k::emit_k(h, k, idx ? idx + i * k : nullptr,
+                                      dist ? dist + i * k : nullptr);
+  if (mean_d) mean_d[i] = o.mean_d;
+  if (mean_d2) mean_d2[i] = o.mean_d2;
 }
 
 // ---------------------------------------------------------------- stats ----
@@ -434,6 +457,26 @@ SampleW carve_sample(void* base, int64_t F) {
   return w;
 }
 
+// The queries' indices in the order of their cell (non-finite rows last): the
+// keys, then a stable LSD radix sort of (cell id, query index) in w.
+const uint32_t* sort_by_cell(const s3k::Grid& g, int64_t cells, const float* q, int64_t m,
+                             const QueryW& w, hipStream_t st) {
+  const int64_t nseg = s3::cdiv(m, kSeg);
+  k_nn_qkeys<<<(unsigned)s3::cdiv(m, kT), kT, 0, st>>>(q, m, g, w.keys[0], w.vals[0]);
+  // the keys are 0 .. cells: as many 8-bit passes as `cells` has bits
+  int bits = 0;
+  while ((cells >> bits) != 0) ++bits;
+  const int passes = (bits + kBits - 1) / kBits;
+  for (int p = 0; p < passes; ++p) {
+    const int src = p & 1, shift = p * kBits;
+    k_nn_hist<<<(unsigned)nseg, kT, 0, st>>>(m, w.keys[src], shift, nseg, w.hist);
+    k_nn_row_scan<<<kBins, kT, 0, st>>>(w.hist, nseg, w.tot);
+    k_nn_scatter<<<(unsigned)nseg, kT, 0, st>>>(m, w.keys[src], w.vals[src], w.keys[1 - src],
+                                                 w.vals[1 - src], shift, nseg, w.hist, w.tot);
+  }
+  return w.vals[passes & 1];
+}
+
 bool is_finite(double v) { return v - v == 0.0; }
 
 // 0: sorted, one thread per query (the product); 1: unsorted; 2: sorted, one
@@ -544,30 +587,77 @@ extern "C" int s3k_query(const void* grid, size_t grid_bytes, int64_t n, const d
   const s3k::Grid g{gw.start, gw.rec, origin[0], origin[1], origin[2], cell, nx, ny, nz};
   hipStream_t st = s3::as_stream(stream);
   const unsigned rows = (unsigned)s3::cdiv(m, kT);
-  const int64_t nseg = s3::cdiv(m, kSeg);
   const int mode = g_query_mode.load();
   if (mode == 1) {
     k_nn_query<<<rows, kT, 0, st>>>(g, q, nullptr, m, max_dist, idx, dist);
     S3_LAUNCH_CHECK();
     return S3_OK;
   }
-  k_nn_qkeys<<<rows, kT, 0, st>>>(q, m, g, w.keys[0], w.vals[0]);
-  // the keys are 0 .. cells: as many 8-bit passes as `cells` has bits
-  int bits = 0;
-  while ((cells >> bits) != 0) ++bits;
-  const int passes = (bits + kBits - 1) / kBits;
-  for (int p = 0; p < passes; ++p) {
-    const int src = p & 1, shift = p * kBits;
-    k_nn_hist<<<(unsigned)nseg, kT, 0, st>>>(m, w.keys[src], shift, nseg, w.hist);
-    k_nn_row_scan<<<kBins, kT, 0, st>>>(w.hist, nseg, w.tot);
-    k_nn_scatter<<<(unsigned)nseg, kT, 0, st>>>(m, w.keys[src], w.vals[src], w.keys[1 - src],
-                                                 w.vals[1 - src], shift, nseg, w.hist, w.tot);
-  }
+  const uint32_t* order = sort_by_cell(g, cells, q, m, w, st);
   if (mode == 2)
-    k_nn_query_wave<<<(unsigned)s3::cdiv(m, kT / 64), kT, 0, st>>>(g, q, w.vals[passes & 1], m,
-                                                                  max_dist, idx, dist);
+    k_nn_query_wave<<<(unsigned)s3::cdiv(m, kT / 64), kT, 0, st>>>(g, q, order, m, max_dist, idx,
+                                                                  dist);
   else
-    k_nn_query<<<rows, kT, 0, st>>>(g, q, w.vals[passes & 1], m, max_dist, idx, dist);
+    k_nn_query<<<rows, kT, 0, st>>>(g, q, order, m, max_dist, idx, dist);
+  S3_LAUNCH_CHECK();
+  return S3_OK;
+}
+
+extern "C" size_t s3k_knn_workspace_bytes(int64_t m) { return s3k_query_workspace_bytes(m); }
+
+extern "C" int s3k_knn(const void* grid, size_t grid_bytes, int64_t n, const double* origin,
+                       double cell, int32_t nx, int32_t ny, int32_t nz, const float* q, int64_t m,
+                       int32_t k, int32_t exclude_self, double max_dist, int32_t* idx, float* dist,
+                       float* mean_d, float* mean_d2, void* workspace, size_t workspace_bytes,
+                       void* stream) {
+  s3::clear_error();
+  if (int e = check_grid_args("s3k_knn", n, origin, cell, nx, ny, nz)) return e;
+  S3_REQUIRE(m >= 0, "s3k_knn: m < 0");
+  S3_REQUIRE(m <= kMaxRows, "s3k_knn: m too large");
+  S3_REQUIRE(k >= 1 && k <= S3K_MAX_K, "s3k_knn: k must be in 1 .. 32, got %d", (int)k);
+  S3_REQUIRE(idx || dist || mean_d || mean_d2, "s3k_knn: every output is null");
+  S3_REQUIRE(!exclude_self || m <= n, "s3k_knn: exclude_self with more queries than rows");
+  S3_REQUIRE(max_dist >= 0.0, "s3k_knn: max_dist must be >= 0 or +inf");
+  S3_REQUIRE(grid && grid_bytes >= s3k_grid_workspace_bytes(n, nx, ny, nz),
+             "s3k_knn: grid workspace too small");
+  S3_REQUIRE(s3::aligned(grid, 256), "s3k_knn: grid must be 256-byte aligned");
+  if (m == 0) return S3_OK;
+  S3_REQUIRE(q, "s3k_knn: null q");
+  S3_REQUIRE(workspace && workspace_bytes >= s3k_knn_workspace_bytes(m),
+             "s3k_knn: workspace too small");
+  S3_REQUIRE(s3::aligned(workspace, 256), "s3k_knn: workspace must be 256-byte aligned");
+  S3_REQUIRE(!s3::overlap(workspace, workspace_bytes, grid, grid_bytes),
+             "s3k_knn: workspace overlaps the grid");
+  {
+    const void* arr[5] = {q, idx, dist, mean_d, mean_d2};
+    const size_t len[5] = {(size_t)m * 12, (size_t)m * k * 4, (size_t)m * k * 4, (size_t)m * 4,
+                           (size_t)m * 4};
+    for (int a = 0; a < 5; ++a) {
+      if (!arr[a]) continue;
+      S3_REQUIRE(!s3::overlap(arr[a], len[a], grid, grid_bytes) &&
+                     !s3::overlap(arr[a], len[a], workspace, workspace_bytes),
+                 "s3k_knn: q or an output overlaps the grid or the workspace");
+      for (int b = a + 1; b < 5; ++b)
+        S3_REQUIRE(!arr[b] || !s3::overlap(arr[a], len[a], arr[b], len[b]),
+                   "s3k_knn: q and the outputs overlap each other");
+    }
+  }
+  const int64_t cells = cells_of_dims(nx, ny, nz);
+  const GridW gw = carve_grid(const_cast<void*>(grid), n, cells);
+  const QueryW w = carve_query(workspace, m);
+  const s3k::Grid g{gw.start, gw.rec, origin[0], origin[1], origin[2], cell, nx, ny, nz};
+  hipStream_t st = s3::as_stream(stream);
+  const unsigned rows = (unsigned)s3::cdiv(m, kT);
+  const uint32_t* order = sort_by_cell(g, cells, q, m, w, st);
+#define S3K_KNN(CAP)                                                                          \
+  k_nn_knn<CAP><<<rows, kT, 0, st>>>(g, q, order, m, k, exclude_self, max_dist, idx, dist, \
+                                     mean_d, mean_d2)
+  // the fewest register slots that hold k
+  if (k <= 4) S3K_KNN(4);
+  else if (k <= 8) S3K_KNN(8);
+  else if (k <= 16) S3K_KNN(16);
+  else S3K_KNN(32);
+#undef S3K_KNN
   S3_LAUNCH_CHECK();
   return S3_OK;
 }

@@ -6,6 +6,8 @@
 // dist2()        squared distance in double, (dx dx + dy dy) + dz dz
 // ring_done(), ring_past()   the two stop rules of the ring walk
 // search()       one query: rings, then the linear rest when they stop paying
+// HitK, insert_k(), search_k(), emit_k()   the same walk keeping the k nearest
+//                rows in registers, and the row it writes
 // face_area(), face_weight(), sample_uniforms(), sample_target(),
 // pick_face(), place()       the sampler
 // Build with -ffp-contract=off: every product and sum rounds once.
@@ -199,6 +201,185 @@ S3K_HD Hit search(const Grid& g, float qxf, float qyf, float qzf, double max_dis
   }
   if (cost) *cost = c;
   return h;
+}
+
+// ---------------------------------------------------- k nearest rows ----
+// The best rows seen so far in ascending (d2, i) order, a total order; an
+// empty slot is (+inf, kNoIndex) and sorts after every row.  CAP is a
+// compile-time constant and every access below is a static index of an
+// unrolled loop, so the slots stay in registers.  All CAP slots are kept
+// sorted whatever k is: the first k of the best CAP are the best k.
+template <int CAP>
+struct HitK {
+  double d2[CAP];
+  int32_t i[CAP];
+};
+
+// what a row of the k-nearest outputs holds beside its slots
+struct RowStats {
+  float mean_d, mean_d2;
+  int32_t filled;
+};
+
+S3K_HD bool before(double d2, int32_t i, double e2, int32_t j) {
+  return d2 < e2 || (d2 == e2 && i < j);
+}
+
+template <int CAP>
+S3K_HD void clear_k(HitK<CAP>& h) {
+#pragma unroll
+  for (int s = 0; s < CAP; ++s) {
+    h.d2[s] = (double)INFINITY;
+    h.i[s] = kNoIndex;
+  }
+}
+
+// slot k - 1, the worst of the k kept: what a candidate has to beat
+template <int CAP>
+S3K_HD void worst_of(const HitK<CAP>& h, int32_t k, double& d2, int32_t& i) {
+  d2 = h.d2[CAP - 1];
+  i = h.i[CAP - 1];
+#pragma unroll
+  for (int s = 0; s < CAP - 1; ++s)
+    if (s == k - 1) {
+      d2 = h.d2[s];
+      i = h.i[s];
+    }
+}
+
+// put (d2, i) in its place; the slots after it move down one, the last is lost
+template <int CAP>
+S3K_HD void insert_k(HitK<CAP>& h, double d2, int32_t i) {
+#pragma unroll
+  for (int s = CAP - 1; s >= 0; --s) {
+    // slot s - 1 still holds its old value here
+    if (before(d2, i, h.d2[s], h.i[s])) {
+      const bool up = s > 0 && before(d2, i, h.d2[s > 0 ? s - 1 : 0], h.i[s > 0 ? s - 1 : 0]);
+      h.d2[s] = up ? h.d2[s > 0 ? s - 1 : 0] : d2;
+      h.i[s] = up ? h.i[s > 0 ? s - 1 : 0] : i;
+    }
+  }
+}
+
+// the records of cells id0 .. id1; rows past the limit and row `self` do not count
+template <int CAP>
+S3K_HD void scan_run_k(const Grid& g, int32_t id0, int32_t id1, double qx, double qy, double qz,
+                       int32_t k, int32_t self, double limit, HitK<CAP>& h, double& w_d2,
+                       int32_t& w_i, Cost& c) {
+  const uint32_t a = g.start[id0], b = g.start[id1 + 1];
+  c.cells += id1 - id0 + 1;
+  c.rows += b - a;
+  for (uint32_t t = a; t < b; ++t) {
+    const Rec r = g.rec[t];
+    const double d2 = dist2(qx, qy, qz, r.x, r.y, r.z);
+    if (r.i != self && d2 <= limit && before(d2, r.i, w_d2, w_i)) {
+      insert_k(h, d2, r.i);
+      worst_of(h, k, w_d2, w_i);
+    }
+  }
+}
+
+// everything outside the cube [x0, x1] x [y0, y1] x [z0, z1] of cells (scan_rest's runs)
+template <int CAP>
+S3K_HD void scan_rest_k(const Grid& g, int32_t x0, int32_t x1, int32_t y0, int32_t y1, int32_t z0,
+                        int32_t z1, double qx, double qy, double qz, int32_t k, int32_t self,
+                        double limit, HitK<CAP>& h, double& w_d2, int32_t& w_i, Cost& c) {
+#define S3K_RUN(A, B) scan_run_k(g, A, B, qx, qy, qz, k, self, limit, h, w_d2, w_i, c)
+  const int32_t slab = g.nx * g.ny;
+  if (z0 > 0) S3K_RUN(0, z0 * slab - 1);
+  for (int32_t z = z0; z <= z1; ++z) {
+    const int32_t zb = z * slab;
+    if (y0 > 0) S3K_RUN(zb, zb + y0 * g.nx - 1);
+    for (int32_t y = y0; y <= y1; ++y) {
+      const int32_t b = zb + y * g.nx;
+      if (x0 > 0) S3K_RUN(b, b + x0 - 1);
+      if (x1 < g.nx - 1) S3K_RUN(b + x1 + 1, b + g.nx - 1);
+    }
+    if (y1 < g.ny - 1) S3K_RUN(zb + (y1 + 1) * g.nx, zb + slab - 1);
+  }
+  if (z1 < g.nz - 1) S3K_RUN((z1 + 1) * slab, g.nz * slab - 1);
+}
+
+// One k-nearest query (include/s3k.h), 1 <= k <= CAP: search()'s walk with k
+// slots.  self: the reference row that does not count (-1: none).  After
+// ring r an unvisited row is at least r cell (1 - 2^-20) away (the argument
+// at the head of this file, which no property of the winner enters), so once
+// slot k - 1 is filled and strictly nearer than that, no unvisited row can
+// come before it, a tie included.  cost may be null.
+template <int CAP>
+S3K_HD void search_k(const Grid& g, float qxf, float qyf, float qzf, int32_t k, int32_t self,
+                     double max_dist, HitK<CAP>& h, Cost* cost) {
+  clear_k(h);
+  Cost c{0, 0, 0, false};
+  double w_d2 = (double)INFINITY;
+  int32_t w_i = kNoIndex;
+  const double limit = max_dist * max_dist;
+  const int64_t kept = (int64_t)g.start[cells_of(g)];
+  if (finite3(qxf, qyf, qzf) && kept > 0) {
+    const double qx = (double)qxf, qy = (double)qyf, qz = (double)qzf;
+    const int32_t cx = cell_axis(qxf, g.ox, g.cell, g.nx), cy = cell_axis(qyf, g.oy, g.cell, g.ny),
+                  cz = cell_axis(qzf, g.oz, g.cell, g.nz);
+    const int32_t reach = imax(imax(imax(cx, g.nx - 1 - cx), imax(cy, g.ny - 1 - cy)),
+                               imax(cz, g.nz - 1 - cz));
+    const int64_t lines = (int64_t)g.ny * g.nz;
+    for (int32_t r = 0;; ++r) {
+      const int32_t x0 = imax(cx - r, 0), x1 = imin(cx + r, g.nx - 1);
+      const int32_t y0 = imax(cy - r, 0), y1 = imin(cy + r, g.ny - 1);
+      const int32_t z0 = imax(cz - r, 0), z1 = imin(cz + r, g.nz - 1);
+      for (int32_t z = z0; z <= z1; ++z) {
+        const bool zface = z - cz == r || cz - z == r;
+        for (int32_t y = y0; y <= y1; ++y) {
+          const int32_t b = (z * g.ny + y) * g.nx;
+          if (zface || y - cy == r || cy - y == r) {
+            S3K_RUN(b + x0, b + x1);
+          } else {
+            if (cx - r >= 0) S3K_RUN(b + cx - r, b + cx - r);
+            if (cx + r <= g.nx - 1) S3K_RUN(b + cx + r, b + cx + r);
+          }
+        }
+      }
+      c.rings = r + 1;
+      if (r >= reach) break;
+      // an empty slot k - 1 is +inf: never done
+      if (ring_done(w_d2, r, g.cell)) break;
+      if (ring_past(r, g.cell, max_dist)) break;
+      if (c.cells >= (kept - c.rows) + lines) {
+        c.linear = true;
+        scan_rest_k(g, x0, x1, y0, y1, z0, z1, qx, qy, qz, k, self, limit, h, w_d2, w_i, c);
+        break;
+      }
+    }
+  }
+#undef S3K_RUN
+  if (cost) *cost = c;
+}
+
+// Write a query's row: slots 0 .. k - 1 to idx / dist (each null or the row's
+// k entries; an empty slot is -1 / +inf) and the means over the filled slots,
+// summed in slot order in double (+inf when none is filled).
+template <int CAP>
+S3K_HD RowStats emit_k(const HitK<CAP>& h, int32_t k, int32_t* idx, float* dist) {
+  double sum_d = 0.0, sum_d2 = 0.0;
+  int32_t filled = 0;
+#pragma unroll
+  for (int s = 0; s < CAP; ++s)
+    if (s < k) {
+      const bool has = h.i[s] != kNoIndex;
+      const double d = sqrt(h.d2[s]);
+      if (has) {
+        sum_d += d;
+        sum_d2 += h.d2[s];
+        ++filled;
+      }
+      if (idx) idx[s] = has ? h.i[s] : -1;
+      if (dist) dist[s] = has ? (float)d : INFINITY;
+    }
+  RowStats o{INFINITY, INFINITY, filled};
+  if (filled > 0) {
+    o.mean_d = (float)(sum_d / (double)filled);
+    o.mean_d2 = (float)(sum_d2 / (double)filled);
+  }
+  return o;
 }
 
 // ------------------------------------------------------------- sampler ----

@@ -244,6 +244,73 @@ class SharedGaussians:
         self._bound = self._compacted_to = m
         return m
 
+    # ---- floaters and plain point clouds (include/s3k.h, splatt3r_amd.nn) ----
+    def remove_outliers(self, k: int = 16, std_ratio: float = 2.0, cell=None) -> int:
+        """Remove the Gaussians whose centre lies far from its neighbours
+        (nn.outlier_mask over means[:n]: the mean distance to the k nearest
+        other centres exceeds the map's mean by std_ratio sample standard
+        deviations), in place: the survivors of the five fields move down in
+        their order (gathered into scratch, copied back, as compact() copies
+        back), the device count is set, and the host bound and the last
+        compaction's result are lowered to it.  `anchors` is untouched.  k
+        and std_ratio are the customary values of statistical outlier
+        removal, not tuned here; cell is the search grid's cell size (default:
+        nn.default_grid).  Two host reads of its own, the count before and
+        the survivors after (the search grid's bounding box is a third,
+        nn.default_grid).  Returns the rows removed; an empty map returns 0."""
+        from splatt3r_amd import nn
+        n = self.n_gaussians
+        if n == 0:
+            return 0
+        keep = nn.outlier_mask(self.means[:n], k, std_ratio, cell)
+        src = keep.nonzero().squeeze(1)
+        m = src.numel()
+        for f in (self.means, self.cov_triu, self.colors, self.opacities, self.kf_id):
+            f[:m] = f[:n][src]
+        self._n.fill_(m)
+        self._bound = m
+        self._compacted_to = min(self._compacted_to, m)
+        return n - m
+
+    def load_points(self, points, colors, kf_idx: int = -1, k: int = 3, opacity: float = 0.1,
+                    scale_min: float = 1e-7) -> int:
+        """Replace the map's content by a plain point cloud (a saved
+        reconstruction, a ground-truth scan, evaluate.load_ply's result):
+        points [n, 3] float32 and colors [n, 3] in [0, 1], device tensors.
+        Every point becomes an isotropic Gaussian as 3DGS initialises one
+        from a point cloud: covariance max(s, scale_min) I with s the mean
+        squared distance to its k nearest other points (nn.knn_scale; a point
+        with no neighbour takes scale_min), the given opacity and kf_id =
+        kf_idx.  Rows with a non-finite coordinate are dropped, and the first
+        max_gaussians of the rest are taken.  Returns the count."""
+        from splatt3r_amd import nn
+        fn = "SharedGaussians.load_points"
+        points = nn._points(points, "points", fn)
+        if not torch.is_tensor(colors) or colors.shape != points.shape:
+            raise ValueError(f"{fn}: colors must be a tensor of points' shape "
+                             f"{tuple(points.shape)}")
+        _lib.require_cuda(colors)
+        ok = torch.isfinite(points).all(1)
+        points = points[ok][:self.max_gaussians].contiguous()
+        colors = colors[ok][:self.max_gaussians].float()
+        n = points.shape[0]
+        self.clear()
+        if n == 0:
+            return 0
+        var = nn.knn_scale(points, k)
+        floor = torch.full_like(var[:1], float(scale_min))         # scale_min as a float32
+        var = torch.maximum(torch.where(torch.isfinite(var), var, floor), floor)
+        self.means[:n] = points
+        self.cov_triu[:n] = 0.0
+        for col in (0, 3, 5):                      # xx, yy, zz
+            self.cov_triu[:n, col] = var
+        self.colors[:n] = colors
+        self.opacities[:n] = float(opacity)
+        self.kf_id[:n] = int(kf_idx)
+        self._n.fill_(n)
+        self._bound = n
+        return n
+
     # ---- 3DGS splat .ply (include/s3w.h, evaluate.write_splat_ply) ----
     def to_splats(self, n: Optional[int] = None, scale_min: float = 1e-7) -> torch.Tensor:
         """The first n Gaussians (default: all, a host read of the count) as

@@ -2,8 +2,12 @@
 mesh sampling (include/s3k.h, csrc/nn_search.hip): what the geometry scores of
 evaluate.eval_reconstruction are reductions of.
 
-  PointGrid     a uniform grid over reference points; .query(q) -> (idx, dist)
-  nearest       build a grid and query it once
+  PointGrid     a uniform grid over reference points; .query(q) -> (idx, dist),
+                .knn(q, k) -> the k nearest rows and their mean distances
+  nearest, knn  build a grid and query it once
+  knn_scale     mean squared distance to the k nearest other points (3DGS's
+                point-cloud initialisation)
+  outlier_mask  statistical outlier removal (map floaters)
   dist_stats    count, sum, sum of squares, count within a threshold, maximum
   sample_mesh   stratified area-uniform samples of a triangle mesh
 
@@ -24,6 +28,8 @@ import torch
 from splatt3r_amd import _abi, _lib
 
 MAX_CELLS = _abi.constants["S3K_MAX_CELLS"]
+MAX_K = _abi.constants["S3K_MAX_K"]
+KNN_OUTPUTS = ("idx", "dist", "mean", "mean_sq")     # s3k_knn's order
 
 
 def _points(t, name: str, fn: str) -> torch.Tensor:
@@ -129,6 +135,51 @@ class PointGrid:
                       idx.data_ptr(), dist.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream(dev))
         return idx, dist
 
+    @torch.no_grad()
+    def knn(self, q, k: int, max_dist: float = math.inf, exclude_self: bool = False,
+            want=("idx", "dist")) -> dict:
+        """The k nearest reference rows (1 <= k <= 32) of every row of q
+        [m, 3], in ascending (distance, index) order; only rows within
+        max_dist count.  Returns a dict of the outputs named in `want`
+        (KNN_OUTPUTS): idx [m, k] int32 and dist [m, k] float32 (-1 and +inf
+        in the slots past the last neighbour), mean and mean_sq [m] float32
+        (the mean distance and mean squared distance to the neighbours found,
+        +inf when there is none).  An output not asked for is not written.
+        exclude_self: q is the grid's own points, and row j is not its own
+        neighbour (by index; needs m <= n)."""
+        fn = "PointGrid.knn"
+        q = _points(q, "q", fn)
+        if q.device != self.ref.device:
+            raise ValueError(f"{fn}: q is on {q.device}, the grid on {self.ref.device}")
+        k = int(k)
+        if not 1 <= k <= MAX_K:
+            raise ValueError(f"{fn}: k must be in 1 .. {MAX_K}, got {k}")
+        max_dist = float(max_dist)
+        if not max_dist >= 0.0:
+            raise ValueError(f"{fn}: max_dist must be >= 0 or +inf, got {max_dist}")
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(w not in KNN_OUTPUTS for w in want):
+            raise ValueError(f"{fn}: want must name at least one of {KNN_OUTPUTS}, got {want}")
+        dev, m = q.device, q.shape[0]
+        if exclude_self and m > self.n:
+            raise ValueError(f"{fn}: exclude_self with {m} queries for {self.n} rows")
+        out = {}
+        for name in KNN_OUTPUTS:
+            if name in want:
+                shape = (m, k) if name in ("idx", "dist") else (m,)
+                out[name] = torch.empty(shape, device=dev, dtype=torch.int32 if name == "idx"
+                                        else torch.float32)
+        if m == 0:              # empty tensors have no address to pass
+            return {name: out[name] for name in want}
+        ptrs = [out[name].data_ptr() if name in out else None for name in KNN_OUTPUTS]
+        ws = _bytes(int(_lib.lib().s3k_knn_workspace_bytes(m)), dev)
+        with torch.cuda.device(dev):
+            _lib.call("s3k_knn", self._grid.data_ptr(), self._grid.numel(), self.n, self._org,
+                      self.cell, *self.dims, q.data_ptr() if m else None, m, k,
+                      1 if exclude_self else 0, max_dist, *ptrs, ws.data_ptr(), ws.numel(),
+                      _lib.stream(dev))
+        return {name: out[name] for name in want}
+
 
 QUERY_MODES = {"sorted": 0, "unsorted": 1, "wave": 2}
 
@@ -144,6 +195,47 @@ def set_query_mode(mode: str = "sorted") -> None:
 def nearest(q, ref, max_dist: float = math.inf, **kw):
     """PointGrid(ref, **kw).query(q, max_dist)."""
     return PointGrid(ref, **kw).query(q, max_dist)
+
+
+def knn(q, ref, k: int, max_dist: float = math.inf, exclude_self: bool = False,
+        want=("idx", "dist"), **kw) -> dict:
+    """PointGrid(ref, **kw).knn(q, k, max_dist, exclude_self, want)."""
+    return PointGrid(ref, **kw).knn(q, k, max_dist, exclude_self, want)
+
+
+def knn_scale(points, k: int = 3, **kw) -> torch.Tensor:
+    """[n] float32: every point's mean squared distance to its k nearest other
+    points, what 3DGS's point-cloud initialisation takes as a Gaussian's
+    squared scale (simple_knn.distCUDA2, k = 3).  +inf for a point with no
+    neighbour.  simple-knn is no dependency of this project: the two follow
+    the same definition, but their parity is not pinned by any test."""
+    return PointGrid(points, **kw).knn(points, k, exclude_self=True, want=("mean_sq",))["mean_sq"]
+
+
+@torch.no_grad()
+def outlier_mask(points, k: int = 16, std_ratio: float = 2.0, cell=None) -> torch.Tensor:
+    """Statistical outlier removal: keep [n] bool, True for the points to keep.
+    With d_i the mean distance of point i to its k nearest other points and
+    mu, sigma the mean and the sample standard deviation (c - 1) of the
+    finite d_i, a point is kept when d_i <= mu + std_ratio sigma; a point
+    with a non-finite coordinate is never kept.  With fewer than two finite
+    d_i every finite point is kept.
+
+    The search is s3k_knn; the threshold is a few torch ops in double on the
+    device from dist_stats' sums (mu = S1 / c, var = max(0, S2 - S1 mu) /
+    (c - 1)), and nothing of it is read back.  k and std_ratio are the
+    customary values, not tuned here.  The sample standard deviation follows
+    Open3D's remove_statistical_outlier; Open3D is no dependency of this
+    project, so parity with it is not pinned by any test."""
+    grid = PointGrid(points, cell=cell)
+    mean = grid.knn(grid.ref, k, exclude_self=True, want=("mean",))["mean"]
+    stats = dist_stats(mean, math.inf)
+    c, s1, s2 = stats[0], stats[1], stats[2]
+    mu = s1 / c
+    var = torch.clamp_min(s2 - s1 * mu, 0.0) / (c - 1.0)
+    thr = mu + float(std_ratio) * torch.sqrt(var)
+    keep = torch.isfinite(mean) & (mean.double() <= thr)
+    return torch.where(c < 2.0, torch.isfinite(grid.ref).all(1), keep)
 
 
 STAT_NAMES = ("count", "sum", "sum_sq", "within", "max")

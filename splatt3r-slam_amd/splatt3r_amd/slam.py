@@ -503,6 +503,23 @@ class Frontend:
                  else self.K.detach().to("cpu", torch.float32).reshape(-1, 3, 3)[0])
             return self.gmap.refine(images, poses, K, iters, **kw)
 
+    def clean_map(self, k=16, std_ratio=2.0):
+        """Remove the map's floaters (SharedGaussians.remove_outliers: the
+        Gaussians whose k nearest neighbours are far for this map) once every
+        queued render has been issued and, where the map follows the poses,
+        it has been re-anchored.  k and std_ratio are the customary values,
+        not tuned.  Never called by the frame loop.  Returns the Gaussians
+        removed, or None when the session keeps no map (viz off)."""
+        self.drain()
+        if self.gmap is None:
+            return None
+        self.sync_map()
+        # on the stream the map's appends were issued on
+        st = self.main_stream if self.main_stream is not None else \
+            torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(st):
+            return self.gmap.remove_outliers(k, std_ratio)
+
     def save_mesh(self, path, voxel, **kw):
         """Write the Gaussian map's surface as a triangle-mesh .ply
         (evaluate.save_mesh: depth rendered from the map at every keyframe's
