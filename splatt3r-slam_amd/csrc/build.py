@@ -81,6 +81,7 @@ SOURCES = {
     "map_reanchor.hip": STRICT,
     "tsdf_mesh.hip": STRICT,
     "nn_search.hip": STRICT,
+    "depth_loss.hip": STRICT,
 }
 
 

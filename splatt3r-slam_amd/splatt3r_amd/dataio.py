@@ -121,6 +121,42 @@ class TUMDataset(MonocularDataset):
                                                            TUM_CALIB[int(m.group(1))])
         if self.camera_intrinsics is None:
             self.use_calibration = False
+        # sensor depth: depth.txt ("timestamp depth/<file>.png") when present,
+        # each RGB frame paired with the nearest depth stamp within 0.02 s
+        self.depth_files: list = [None] * len(self.rgb_files)
+        if (self.root / "depth.txt").exists():
+            from splatt3r_amd.evaluate import associate
+            drows = []
+            with open(self.root / "depth.txt") as f:
+                for line in f:
+                    if line.startswith("#") or not line.strip():
+                        continue
+                    t, path = line.split()[:2]
+                    drows.append((float(t), self.root / path))
+            ia, ib = associate(self.timestamps, [t for t, _ in drows], 0.02)
+            for i, j in zip(ia.tolist(), ib.tolist()):
+                self.depth_files[i] = drows[j][1]
+
+    DEPTH_FACTOR = 5000.0          # TUM: a 16-bit PNG value of 5000 is 1 m, 0 is no reading
+
+    def read_depth(self, idx) -> Optional[np.ndarray]:
+        """The sensor depth of RGB frame idx in metres, float32 [H, W] at the
+        sensor's resolution with 0 where there is no reading
+        (ingest.resize_depth brings it to the network's geometry), or None
+        when the frame has no depth partner (or the sequence no depth.txt).
+        A sequence read undistorted has no depth: undistorting depth is not
+        done here."""
+        if self.use_calibration:
+            raise NotImplementedError(
+                "TUMDataset.read_depth: the sequence is read undistorted (use_calib); "
+                "undistorting depth is not implemented")
+        path = self.depth_files[idx]
+        if path is None:
+            return None
+        from PIL import Image
+        with Image.open(path) as im:
+            raw = np.asarray(im)
+        return raw.astype(np.float32) / np.float32(self.DEPTH_FACTOR)
 
 
 class EurocDataset(MonocularDataset):
@@ -214,14 +250,33 @@ def write_synthetic_euroc(root, n: int, seed: int = 0, step_px: float = 2.5) -> 
 
 
 def write_synthetic_tum(root, n: int, H: int = 480, W: int = 640, seed: int = 0,
-                        step_px: float = 2.5) -> pathlib.Path:
+                        step_px: float = 2.5, depth: bool = False) -> pathlib.Path:
     """A TUM-layout sequence of n H x W PNG frames panning over a smooth
     multi-scale texture (synthetic.tum_like_sequence's generator at the
-    camera's native 640x480, before resize_img)."""
+    camera's native 640x480, before resize_img).
+
+    depth=True also writes the sensor depth of that planar scene, as TUM
+    ships it: depth/<t>.png (16-bit, 5000 per metre, 0 for no reading) and
+    depth.txt, stamped 5 ms after the colour frames.  The plane is 2 m away
+    and tilted by 0.25 m across the image width, and an 8-pixel band on the left
+    has no reading (the shadow of a real sensor's baseline).  The other
+    files are the same bytes with and without it."""
     from PIL import Image
     from splatt3r_amd.synthetic import smooth_texture
     root = pathlib.Path(root)
     (root / "rgb").mkdir(parents=True, exist_ok=True)
+    if depth:
+        (root / "depth").mkdir(parents=True, exist_ok=True)
+        plane = np.broadcast_to(2.0 + 0.25 * np.arange(W, dtype=np.float64) / W, (H, W))
+        raw = np.round(plane * TUMDataset.DEPTH_FACTOR).astype(np.uint16)
+        raw[:, :8] = 0
+        dlines = ["# depth maps", "# synthetic TUM-layout sequence", "# timestamp filename"]
+        for i in range(n):
+            t = 1305031102.175304 + i / 30.0 + 0.005
+            name = f"depth/{t:.6f}.png"
+            Image.fromarray(raw).save(root / name, compress_level=1)
+            dlines.append(f"{t:.6f} {name}")
+        (root / "depth.txt").write_text("\n".join(dlines) + "\n")
     pad = int(np.ceil(step_px * n)) + 8
     tex = smooth_texture(H + pad, W + pad, seed)           # [3, H', W'] in [0, 1]
     lines = ["# color images", "# synthetic TUM-layout sequence", "# timestamp filename"]

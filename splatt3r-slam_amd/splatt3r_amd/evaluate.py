@@ -744,3 +744,41 @@ def load_geometry_metrics(path):
             if k in d:
                 d[k] = np.asarray(d[k], np.float64)
     return m
+
+
+# ------------------------------------------------------- rendered depth ----
+def eval_depth_renders(gmap, T_WC, K, targets, weights=None, align="global", alpha_min=0.5):
+    """Score the map's rendered depth against target depth on the device
+    (depth.depth_metrics: abs-rel, sq-rel, RMSE, RMSE-log, L1, delta < 1.25^k).
+    gmap: a SharedGaussians; T_WC [V, 4, 4] camera-to-world (s R | t);
+    targets, weights: [V, H, W] (weights or None), in each view's camera
+    units.  align: None, "scale" (one least-squares scale per view) or
+    "global" (one for all views; the default, as a monocular map's scale is
+    free).  Returns one dict of depth.METRIC_NAMES per view (one host read),
+    or None for an empty map."""
+    from splatt3r_amd.depth import METRIC_NAMES, depth_metrics
+    V, H, W = targets.shape
+    out = gmap.render_depth_alpha(T_WC, K, H, W)
+    if out is None:
+        return None
+    f = lambda t: None if t is None else t.to(gmap.device, torch.float32).contiguous()
+    m = depth_metrics(out[0], out[1], f(targets), f(weights), align=align, alpha_min=alpha_min)
+    host = torch.stack([m[k] for k in METRIC_NAMES]).cpu().tolist()
+    return [{k: host[j][i] for j, k in enumerate(METRIC_NAMES)} for i in range(V)]
+
+
+def save_depth_metrics(logdir, logfile, rows):
+    """Write the rows eval_depth_renders / Frontend.eval_depth returns as one
+    JSON line (a list of dicts; NaN as JSON's NaN literal)."""
+    import json
+    logdir = pathlib.Path(logdir)
+    logdir.mkdir(exist_ok=True, parents=True)
+    with open(logdir / logfile, "w") as f:
+        f.write(json.dumps([{k: float(v) for k, v in r.items()} for r in rows]) + "\n")
+
+
+def load_depth_metrics(path):
+    """Reader for the files save_depth_metrics writes: the list of dicts."""
+    import json
+    with open(path) as f:
+        return json.loads(f.readline())

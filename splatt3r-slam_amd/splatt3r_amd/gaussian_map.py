@@ -470,6 +470,39 @@ class SharedGaussians:
                     rasterizer_intrinsics(settings[0]))
 
     @torch.no_grad()
+    def render_depth_alpha(self, T_WC, K, H, W, near: float = 0.1, far: float = 1000.0,
+                           n: Optional[int] = None):
+        """render_depths' render without its division and threshold, for
+        splatt3r_amd.depth: (depth [V, H, W] = sum z alpha T with the
+        scale-invariant factor undone, i.e. in each view's camera units, alpha
+        [V, H, W] = sum alpha T), or None for an empty map.  depth / alpha is
+        the expected depth where alpha is large enough to trust."""
+        from diff_gaussian_rasterization import GaussianRasterizer
+        from splatt3r_amd.refine import _cameras
+        if n is None:
+            n = self.n_gaussians
+        if n == 0:
+            return None
+        dev = self.device
+        T_WC = torch.as_tensor(T_WC).reshape(-1, 4, 4)
+        with torch.cuda.device(dev):
+            settings, s = _cameras(T_WC, K, H, W, near, far, None, dev)
+            sc_means = torch.empty(n, 3, device=dev)
+            sc_cov = torch.empty(n, 6, device=dev)
+            _lib.call("s3w_map_scale", self.means.data_ptr(), self.cov_triu.data_ptr(),
+                      self._n.data_ptr(), n, s, s * s, sc_means.data_ptr(), sc_cov.data_ptr(),
+                      _lib.stream(dev))
+            depths, alphas = [], []
+            for st in settings:
+                out = GaussianRasterizer(st)(
+                    means3D=sc_means, means2D=torch.zeros_like(sc_means), shs=None,
+                    colors_precomp=self.colors[:n], opacities=self.opacities[:n, None],
+                    cov3D_precomp=sc_cov, return_depth=True)
+                depths.append(out[2] / s)
+                alphas.append(out[3])
+            return torch.stack(depths).contiguous(), torch.stack(alphas).contiguous()
+
+    @torch.no_grad()
     def extract_mesh(self, T_WC, K, H, W, voxel, bounds=None, alpha_min: float = 0.5,
                      near: float = 0.1, far: float = 1000.0, w_min: float = 1.0,
                      view_batch: int = 16, **volume_kw):

@@ -53,6 +53,23 @@ def ingest_geometry(in_h: int, in_w: int, size: int, square_ok: bool = False):
     return (W, H), filt, box, (W1 / W, H1 / H, (W - cw) / 2, (H - ch) / 2)
 
 
+def resize_depth(depth_hw, size: int = 512) -> np.ndarray:
+    """A depth image [H, W] brought to the geometry resize_img gives the
+    camera image of the same size (ingest_geometry: resize, then centre
+    crop), sampled nearest on the host: output pixel (x, y) of the resized
+    image takes source pixel (floor((x + 0.5) in_w / W), floor((y + 0.5)
+    in_h / H)), Pillow's NEAREST rule.  Depth is never blended across a
+    discontinuity, and an invalid value (0) stays what it is.  float32."""
+    d = np.asarray(depth_hw)
+    if d.ndim != 2:
+        raise ValueError(f"resize_depth: depth must be [H, W], got {d.shape}")
+    in_h, in_w = d.shape
+    (W, H), _, box, _ = ingest_geometry(in_h, in_w, size)
+    xs = np.minimum(((np.arange(box[0], box[2]) + 0.5) * (in_w / W)).astype(np.int64), in_w - 1)
+    ys = np.minimum(((np.arange(box[1], box[3]) + 0.5) * (in_h / H)).astype(np.int64), in_h - 1)
+    return np.ascontiguousarray(d[ys[:, None], xs[None, :]], dtype=np.float32)
+
+
 # ----------------------------------------------------------------- tables --
 def _sinc(x: float) -> float:
     if x == 0.0:

@@ -8,6 +8,8 @@
                  not touch
   refine_splats  the loop: activate, render, photometric loss, backward, step
   render_splats  the images that loop compares against its targets
+  DepthControl   a depth term for that loop: the rendered depth against target
+                 depth (splatt3r_amd.depth, include/s3z.h)
   pose_gradient  dL/dpose of one view, reduced from the rasterizer's
                  per-Gaussian gradients (include/s3x.h, csrc/pose_grad.hip)
   PoseControl    Adam on the camera twists, fused with the retraction and the
@@ -416,6 +418,74 @@ class DensityControl:
         return new_stats(opt.rows14.shape[0], opt.rows14.device)
 
 
+class DepthControl:
+    """Depth supervision of refine_splats (splatt3r_amd.depth, include/s3z.h):
+    each step's view is rendered with return_depth=True and
+    weight x depth_loss(rendered depth / alpha against targets[v]) is added to
+    the photometric loss before the single backward.
+
+    targets [V, H, W]: the target depth of every view, in the units of T_WC's
+    cameras (view-space z); a pixel with no target is 0 (or NaN).  weights
+    [V, H, W] or None: per-pixel weights, a mask being 0 / 1.  scale: a number
+    the rendered depth is multiplied by before it is compared (None: 1).
+    l1_weight, l2_weight, grad_weight and alpha_min are depth_loss's.
+
+    weight = 0.1 is MonoGS's RGB-D split (0.9 photometric, 0.1 depth); nobody
+    has tuned it for this map.
+
+    After a run: .history holds the per-step depth losses (before `weight`),
+    a device tensor [iters]."""
+
+    def __init__(self, targets, weights=None, weight: float = 0.1, l1_weight: float = 1.0,
+                 l2_weight: float = 0.0, grad_weight: float = 0.0, alpha_min: float = 0.5,
+                 scale=None):
+        for name, t in (("targets", targets), ("weights", weights)):
+            if t is None and name == "weights":
+                continue
+            if not torch.is_tensor(t) or t.dim() != 3 or not t.is_floating_point():
+                raise ValueError(f"DepthControl: {name} must be a floating-point [V, H, W] tensor")
+        if weights is not None and weights.shape != targets.shape:
+            raise ValueError(f"DepthControl: weights {tuple(weights.shape)} and targets "
+                             f"{tuple(targets.shape)} differ in shape")
+        vals = dict(weight=weight, l1_weight=l1_weight, l2_weight=l2_weight,
+                    grad_weight=grad_weight, alpha_min=alpha_min)
+        for k, v in vals.items():
+            if not (float(v) >= 0.0 and math.isfinite(float(v))):
+                raise ValueError(f"DepthControl: {k} must be >= 0 and finite, got {v}")
+        if scale is not None and not (float(scale) > 0.0 and math.isfinite(float(scale))):
+            raise ValueError(f"DepthControl: scale must be > 0 and finite, got {scale}")
+        self.targets, self.weights = targets, weights
+        self.weight, self.l1_weight, self.l2_weight = float(weight), float(l1_weight), float(l2_weight)
+        self.grad_weight, self.alpha_min = float(grad_weight), float(alpha_min)
+        self.scale = 1.0 if scale is None else float(scale)
+        self.history: Optional[torch.Tensor] = None
+
+    def check(self, V: int, H: int, W: int) -> None:
+        if tuple(self.targets.shape) != (V, H, W):
+            raise ValueError(f"DepthControl: targets must be [{V}, {H}, {W}], got "
+                             f"{tuple(self.targets.shape)}")
+
+    def begin(self, iters: int, render_scale: float, device) -> None:
+        """Start a run: targets and weights move to the device, and the
+        scale-invariant factor of the cameras (the rasterizer's depth is
+        render_scale x the caller's units) is folded into the kernel's scale."""
+        f = lambda t: None if t is None else t.detach().to(device, torch.float32).contiguous()
+        self._targets, self._weights = f(self.targets), f(self.weights)
+        self._scale = torch.full((1,), self.scale / float(render_scale), dtype=torch.float32,
+                                 device=device)
+        self.history = torch.zeros(int(iters), device=device, dtype=torch.float32)
+
+    def loss(self, it: int, v: int, depth, alpha):
+        """The depth loss of view v's render (before `weight`); recorded."""
+        from splatt3r_amd.depth import depth_loss
+        out = depth_loss(depth[None], alpha[None], self._targets[v:v + 1],
+                         None if self._weights is None else self._weights[v:v + 1],
+                         scale=self._scale, l1_weight=self.l1_weight, l2_weight=self.l2_weight,
+                         grad_weight=self.grad_weight, alpha_min=self.alpha_min)
+        self.history[it] = out.detach()
+        return out
+
+
 def _cameras(T_WC, K, H, W, near, far, bg, dev):
     """render.camera_settings (scale-invariant) of V camera-to-world poses:
     the intrinsics-only quantities on the host (no device read for the
@@ -449,7 +519,7 @@ def render_splats(rows14, T_WC, K, H, W, near=0.1, far=1000.0, bg=None):
 
 def refine_splats(rows14, images, T_WC, K, iters, masks=None, l1_weight=0.8, ssim_weight=0.2,
                   mse_weight=0.0, near=0.1, far=1000.0, bg=None, sparse=True, order=None,
-                  density=None, poses=None, **lr):
+                  density=None, poses=None, depth=None, **lr):
     """Fit splat rows to images.  rows14 [n, 14] float32 on the GPU (a copy is
     refined; the argument is left as it is), images [V, 3, H, W] in [0, 1],
     T_WC [V, 4, 4] camera-to-world, K [3, 3] pixel intrinsics, masks
@@ -474,12 +544,29 @@ def refine_splats(rows14, images, T_WC, K, iters, masks=None, l1_weight=0.8, ssi
     poses are poses.T_WC.  Rows and poses together have a 6-dof gauge: fix a
     view, PoseControl(fixed=(0,)).
 
+    depth: a DepthControl, or None for the photometric loss alone (the same
+    launches and the same bits as before the argument existed).  With one,
+    the step renders with return_depth=True and adds depth.weight x
+    depth.depth_loss of the rendered depth and alpha against depth.targets[v]
+    to the loss before the one backward; the cameras' scale-invariant factor
+    goes into the kernel's scale argument, no tensor is rescaled.  history is
+    the total loss, depth.history the depth term.  Not together with poses
+    (NotImplementedError): the pose gradient is not taken through the depth.
+
     Returns (rows14, history): the refined rows and the per-step losses
     [iters] as a device tensor (the loss before each step).  Without density
     the loop itself reads nothing back from the device (the rasterizer's
     forward reads its instance count, as in every differentiable render)."""
     from diff_gaussian_rasterization import GaussianRasterizer
     from splatt3r_amd.photometric import photometric_loss
+    if depth is not None:
+        if not isinstance(depth, DepthControl):
+            raise TypeError("refine_splats: depth must be a DepthControl or None")
+        if poses is not None:
+            raise NotImplementedError("refine_splats: depth= together with poses= is not "
+                                      "implemented")
+        if torch.is_tensor(images) and images.dim() == 4:
+            depth.check(images.shape[0], *images.shape[-2:])
     _check_rows(rows14, "refine_splats")
     dev = rows14.device
     if images.dim() != 4 or images.shape[1] != 3:
@@ -514,6 +601,8 @@ def refine_splats(rows14, images, T_WC, K, iters, masks=None, l1_weight=0.8, ssi
         else:
             settings, s = _pose_cameras(poses, T_WC, K, H, W, near, far, bg, dev)
         stats = None if density is None else new_stats(rows.shape[0], dev)
+        if depth is not None:
+            depth.begin(iters, s, dev)
         for it in range(int(iters)):
             v = order[it % len(order)]
             acts = [t.requires_grad_(True) for t in activate(opt.rows14, s)]
@@ -521,13 +610,20 @@ def refine_splats(rows14, images, T_WC, K, iters, masks=None, l1_weight=0.8, ssi
             means2D = torch.zeros_like(means3D)
             if density is not None:
                 means2D.requires_grad_(True)
-            img, radii = GaussianRasterizer(settings[v])(
-                means3D=means3D, means2D=means2D, opacities=opac, shs=shs,
-                scales=scales, rotations=rots)
+            if depth is None:
+                img, radii = GaussianRasterizer(settings[v])(
+                    means3D=means3D, means2D=means2D, opacities=opac, shs=shs,
+                    scales=scales, rotations=rots)
+            else:
+                img, radii, zmap, amap = GaussianRasterizer(settings[v])(
+                    means3D=means3D, means2D=means2D, opacities=opac, shs=shs,
+                    scales=scales, rotations=rots, return_depth=True)
             loss = photometric_loss(img[None], images[v:v + 1],
                                     None if masks is None else masks[v:v + 1],
                                     mse_weight=mse_weight, l1_weight=l1_weight,
                                     ssim_weight=ssim_weight)
+            if depth is not None:
+                loss = loss + depth.weight * depth.loss(it, v, zmap, amap)
             loss.backward()
             history[it] = loss.detach()
             if poses is not None and v not in poses.fixed:

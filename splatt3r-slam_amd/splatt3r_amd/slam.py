@@ -475,7 +475,15 @@ class Frontend:
         with torch.cuda.stream(st):
             return save_gaussian_splats(path.parent, path.name, self.gmap)
 
-    def refine_map(self, iters, **kw):
+    def _own_depth(self, kfs, h, w, conf_min, dev):
+        """Every keyframe's own pointmap as depth supervision: (targets
+        [V, h, w] = X_canon's z, weights [V, h, w] = 1 where the average
+        confidence exceeds conf_min, else 0)."""
+        z = torch.stack([kf.X_canon[:, 2].reshape(h, w) for kf in kfs]).to(dev, torch.float32)
+        c = torch.stack([kf.get_average_conf().reshape(h, w) for kf in kfs]).to(dev)
+        return z.contiguous(), (c > conf_min).to(torch.float32).contiguous()
+
+    def refine_map(self, iters, depth=None, depth_weights=None, conf_min=1.5, **kw):
         """Fit the Gaussian map to the keyframes' camera images
         (SharedGaussians.refine) once every queued render has been issued:
         image evaluate.keyframe_target(kf), pose the 4 x 4 (s R | t) of
@@ -483,8 +491,18 @@ class Frontend:
         evaluate.eval_novel_view_renders takes them.  **kw goes to
         refine.refine_splats.  Never called by the frame loop.  Returns the
         per-step losses (device tensor), or None when the session keeps no
-        map (viz off), the map is empty or there is no keyframe."""
+        map (viz off), the map is empty or there is no keyframe.
+
+        depth: None (photometric only), a refine.DepthControl, a [V, h, w]
+        tensor of target depth per keyframe in that keyframe's own units
+        (with depth_weights, [V, h, w] or None), or "own": each keyframe's
+        pointmap z (kf.X_canon[:, 2]) weighted 1 where kf.get_average_conf()
+        exceeds conf_min and 0 elsewhere.  conf_min's default is the
+        reference's C_conf_threshold, the value its save_reconstruction is
+        called with.  With (s R | t) poses view-space z is in the keyframe's
+        own units, so no scale enters."""
         from splatt3r_amd.evaluate import keyframe_target
+        from splatt3r_amd.refine import DepthControl
         from splatt3r_amd.splatt3r_utils import _estimate_default_intrinsics
         self.drain()
         if self.gmap is None or len(self.keyframes) == 0:
@@ -501,7 +519,48 @@ class Frontend:
             h, w = images.shape[-2:]
             K = (_estimate_default_intrinsics(h, w, "cpu") if self.K is None
                  else self.K.detach().to("cpu", torch.float32).reshape(-1, 3, 3)[0])
+            if isinstance(depth, str):
+                if depth != "own":
+                    raise ValueError(f"refine_map: depth must be None, 'own', a tensor or a "
+                                     f"DepthControl, got {depth!r}")
+                depth = DepthControl(*self._own_depth(kfs, h, w, conf_min, dev))
+            elif torch.is_tensor(depth):
+                depth = DepthControl(depth, depth_weights)
+            if depth is not None:
+                kw["depth"] = depth
             return self.gmap.refine(images, poses, K, iters, **kw)
+
+    def eval_depth(self, targets, weights=None, **kw):
+        """Score the map's rendered depth at every keyframe's pose against
+        `targets` ([V, h, w], one per keyframe, in that keyframe's own units;
+        "own": the keyframes' pointmap z with weights from conf_min, as
+        refine_map(depth="own") builds them) once every queued render has been
+        issued (evaluate.eval_depth_renders, which takes **kw: align,
+        alpha_min).  Never called by the frame loop.  Returns one dict of
+        depth.METRIC_NAMES per keyframe, or None when the session keeps no map
+        (viz off), the map is empty or there is no keyframe."""
+        from splatt3r_amd.evaluate import eval_depth_renders, keyframe_target
+        from splatt3r_amd.splatt3r_utils import _estimate_default_intrinsics
+        self.drain()
+        if self.gmap is None or len(self.keyframes) == 0:
+            return None
+        self.sync_map()
+        # on the stream the map's appends were issued on
+        st = self.main_stream if self.main_stream is not None else \
+            torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(st):
+            dev = self.gmap.device
+            kfs = [self.keyframes[i] for i in range(len(self.keyframes))]
+            poses = torch.cat([_sim3_to_4x4(kf.T_WC).to(dev).reshape(1, 4, 4) for kf in kfs])
+            h, w = keyframe_target(kfs[0]).shape[-2:]
+            K = (_estimate_default_intrinsics(h, w, "cpu") if self.K is None
+                 else self.K.detach().to("cpu", torch.float32).reshape(-1, 3, 3)[0])
+            if isinstance(targets, str):
+                if targets != "own":
+                    raise ValueError(f"eval_depth: targets must be 'own' or a tensor, got "
+                                     f"{targets!r}")
+                targets, weights = self._own_depth(kfs, h, w, kw.pop("conf_min", 1.5), dev)
+            return eval_depth_renders(self.gmap, poses, K, targets, weights, **kw)
 
     def clean_map(self, k=16, std_ratio=2.0):
         """Remove the map's floaters (SharedGaussians.remove_outliers: the
